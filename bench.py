@@ -18,7 +18,14 @@ touches the GPU itself) and relays rank 0's JSON line.  Either way a world that 
 not N ranks is an error, and the line carries `rccl_world` and every rank's
 ms_per_step.
 
-Also reported (secondary lines in the same JSON object):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs:
+it builds the workload (seeded: the same arguments give the same inputs on every run), warms
+up, times the N steps, checks the verdicts against the tamper map and prints the result line.
+`--dump-outputs DIR` also writes what the last timed step returned to its caller, the verdict
+array, as DIR/verdicts.npy (float32, 1.0 = valid; verdicts_rank<r>.npy with several ranks), so
+two builds can be compared output for output.  Everything below runs only with `--full`.
+
+Also reported with `--full` (secondary lines in the same JSON object):
 - "aggregation": committee pubkey aggregation alone (1024 committees x 128);
 - "c3_epoch": one epoch of attestations per GPU -- per committee
   bls_aggregate_pubkeys(128 pks) + bls_aggregate_pubkeys([]) +
@@ -70,6 +77,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--n", type=int, default=1 << 16, help="verifies per rank per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the roofline, the no-events rerun, the CPU baselines and the "
+                         "secondary lines (the options below choose among them); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed step to DIR/verdicts.npy (float32)")
     ap.add_argument("--committees", type=int, default=1024)
     ap.add_argument("--committee-size", type=int, default=128)
     ap.add_argument("--cpu-sample", type=int, default=256)
@@ -96,7 +108,28 @@ def parse():
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)   # launcher test hook
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: the ranks join a gloo world, report it and exit")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.sections and not args.full:
+        ap.error("--sections chooses among the secondary lines, which run only with --full")
+    return args
+
+
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, seed=0xB15_00D0):
+    """--dump-outputs: each array as <directory>/<name>.npy in float32, at most MAX_DUMP_BYTES in
+    all; a larger array is cut to a fixed, seeded sample of its elements (the same indices on
+    every run, in ascending order)."""
+    os.makedirs(directory, exist_ok=True)
+    budget = MAX_DUMP_BYTES // 4 // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a).astype(np.float32).reshape(-1)
+        if a.size > budget:
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, budget, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _free_port():
@@ -1081,6 +1114,8 @@ def main():
     for v in vers:
         v.zero_()
     torch.cuda.synchronize()
+    # the headline is timed with the per-launch HIP events on, with or without --full, so that `value`
+    # is one figure across both kinds of run and across rounds (--full's roofline reads the events)
     native.profile_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -1105,6 +1140,43 @@ def main():
         elapsed = max(float(x.item()) for x in allt)
     total_items = n * args.steps * world
     value = total_items / elapsed
+    if args.dump_outputs:
+        # what the last timed step handed back: its verdict buffer (checked above)
+        last = vers[(args.steps - 1) % kin].cpu().numpy()
+        dump_outputs(args.dump_outputs, {"verdicts" if world == 1 else "verdicts_rank%d" % rank: last})
+
+    # ---------------- the headline's line (rank 0)
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "BLS sig verifications/sec (whole node)",
+            "value": round(value, 2),
+            "unit": "verifications/s",
+            "n_gpus": world,
+            "rccl_world": dist.get_world_size() if world > 1 else 1,
+            "rank_ms_per_step": [round(x, 3) for x in rank_ms],
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32 (381-bit Montgomery, 14x28-bit limbs in u32 words)",
+            "data": "synthetic (random keys/messages, signatures made on device)",
+            "config": {"workload": "C2: %d independent bls_verify deposit PoP checks per GPU (domain=3, 1/16 tampered)" % n,
+                       "global_batch": n * world, "parallelism": "dp%d (independent items, no collective)" % world,
+                       "batches_in_flight": kin,
+                       "subgroup_policy": args.policy},
+        }
+    if not args.full:
+        # a plain run ends here: the headline alone
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---------------- everything from here on runs only with --full
     # the same K steps again with the per-launch HIP events off (the headline keeps
     # the events, which the roofline's kernel times come from; this shows what they cost)
     if world > 1:
@@ -1190,9 +1262,8 @@ def main():
         agg["registry"] = bench_registry_c3(native, L, args, pks, idx, offsets, d_out, world, dist, dev, stream, t_u8)
         return agg
 
-    # ---------------- the headline's line (rank 0): roofline of the dominant kernel from the timed
-    # steps' own HIP-event profile
-    line = None
+    # ---------------- the headline's roofline (rank 0): the dominant kernel from the timed steps'
+    # own HIP-event profile
     if rank == 0:
         counts = count_fp_muls(pks, msgs, sigs, doms, strict=int(args.policy == "strict"))
         kern_ms = stage_times(prof, args.steps)   # ms per step of each stage (each kernel once per step)
@@ -1217,28 +1288,8 @@ def main():
         roofline["pipeline_frac"] = round(whole / peak, 4) if peak else None
         roofline["issue"] = issue_roofline(dom_kernels, n, kern_ms[dom_k])
         roofline["occupancy_ceiling"] = mac_stream_ceiling(achieved, peak)
-        line = {
-            "metric": "BLS sig verifications/sec (whole node)",
-            "value": round(value, 2),
-            "unit": "verifications/s",
-            "n_gpus": world,
-            "rccl_world": dist.get_world_size() if world > 1 else 1,
-            "rank_ms_per_step": [round(x, 3) for x in rank_ms],
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32 (381-bit Montgomery, 14x28-bit limbs in u32 words)",
-            "data": "synthetic (random keys/messages, signatures made on device)",
-            "config": {"workload": "C2: %d independent bls_verify deposit PoP checks per GPU (domain=3, 1/16 tampered)" % n,
-                       "global_batch": n * world, "parallelism": "dp%d (independent items, no collective)" % world,
-                       "batches_in_flight": kin,
-                       "subgroup_policy": args.policy},
-            "roofline": roofline,
-            "no_profiling_events": no_events,
-        }
+        line["roofline"] = roofline
+        line["no_profiling_events"] = no_events
 
     # ---------------- secondary lines (other policy, C3 aggregation, deposits, randomized, C3-C5,
     # RCCL, latency), after the headline and guarded: an error is recorded in the line instead of

@@ -44,3 +44,40 @@ def test_launcher_ends_the_other_ranks_when_one_fails():
     assert r.returncode != 0
     assert "rank exit codes" in r.stderr
     assert time.time() - t0 < 120
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """`--full` is off unless given; the secondary lines it guards cannot be asked for without it."""
+    import bench
+    import pytest
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--sections", "c3", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.sections == "c3" and a.dump_outputs == "d"
+    for bad in (["--sections", "c3"], ["--steps", "0"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit) as e:
+            bench.parse()
+        assert e.value.code == 2
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: <name>.npy per array, float32, the same bytes on every run; an output over
+    the cap is cut to a fixed sample (same indices each time, ascending)."""
+    import numpy as np
+    import bench
+    v = (np.arange(1000) % 16 != 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"verdicts": v})
+    got = np.load(tmp_path / "a" / "verdicts.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    assert (tmp_path / "a" / "verdicts.npy").read_bytes() == (tmp_path / "b" / "verdicts.npy").read_bytes()
+    monkeypatch.setattr(bench, "MAX_DUMP_BYTES", 4 * 100)
+    x = np.arange(1000)
+    for d in ("c", "e"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x})
+    s = np.load(tmp_path / "c" / "x.npy")
+    assert s.dtype == np.float32 and s.size == 100 and np.all(np.diff(s) > 0) and set(s) <= set(x.astype(np.float32))
+    assert np.array_equal(s, np.load(tmp_path / "e" / "x.npy"))

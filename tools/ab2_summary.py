@@ -1,12 +1,14 @@
-"""Summary of tools/ab_variants.sh secondary runs: python tools/ab2_summary.py TAG variant..."""
+"""Summary of tools/ab_variants_full.sh secondary runs (read from $OUT, default bench_out, as the
+script writes them): python tools/ab2_summary.py TAG variant..."""
 import json
+import os
 import sys
 
 tag, vs = sys.argv[1], sys.argv[2:]
 for r in (1, 2, 3):
     for v in vs:
         try:
-            d = json.loads(open(f"gpurun_out/ab2_{tag}_{v}_{r}.json").read().splitlines()[-1])
+            d = json.loads(open(os.path.join(os.environ.get("OUT", "bench_out"), f"ab2_{tag}_{v}_{r}.json")).read().splitlines()[-1])
         except OSError:
             continue
         rb = d.get("c2_randomized_batch", {}).get("by_sub_batch", {})

@@ -4,14 +4,14 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 TAG=${1:-rb}; SIZES=${2:-8,16,64}
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "randomized" -p no:cacheprovider --timeout 120 --timeout-method thread > gpurun_out/rb_tests_$TAG.log 2>&1 || { tail -30 gpurun_out/rb_tests_$TAG.log; exit 1; }
-tail -2 gpurun_out/rb_tests_$TAG.log
-timeout -k 10 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-aggregate --no-secondary --sections randomized --rb-batch $SIZES > gpurun_out/rb_$TAG.json 2> gpurun_out/rb_$TAG.err || { tail -5 gpurun_out/rb_$TAG.err; exit 1; }
+timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "randomized" -p no:cacheprovider --timeout 120 --timeout-method thread > $OUT/rb_tests_$TAG.log 2>&1 || { tail -30 $OUT/rb_tests_$TAG.log; exit 1; }
+tail -2 $OUT/rb_tests_$TAG.log
+timeout -k 10 400 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-aggregate --no-secondary --sections randomized --rb-batch $SIZES > $OUT/rb_$TAG.json 2> $OUT/rb_$TAG.err || { tail -5 $OUT/rb_$TAG.err; exit 1; }
 python - <<PY
 import json
-d = json.loads(open("gpurun_out/rb_$TAG.json").read().splitlines()[-1])
+d = json.loads(open("$OUT/rb_$TAG.json").read().splitlines()[-1])
 print("default", round(d["value"]), {k: round(v, 2) for k, v in d["roofline"]["kernel_avg_ms"].items()})
 r = d["c2_randomized_batch"]
 for k, v in (r.get("by_sub_batch") or {r["sub_batch"]: r}).items():

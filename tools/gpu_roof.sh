@@ -5,10 +5,10 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 TAG=${1:-roof}
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 180 ./tools/valu_peak > gpurun_out/valu_peak_$TAG.json \
- && cp gpurun_out/valu_peak_$TAG.json profiles/valu_peak_r04.json && echo "valu_peak ok" \
- && timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-secondary --no-cpu-baseline --no-aggregate > gpurun_out/qb_$TAG.json 2> gpurun_out/qb_$TAG.err \
+timeout -k 10 180 ./tools/valu_peak > $OUT/valu_peak_$TAG.json \
+ && cp $OUT/valu_peak_$TAG.json profiles/valu_peak_r04.json && echo "valu_peak ok" \
+ && timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-secondary --no-cpu-baseline --no-aggregate > $OUT/qb_$TAG.json 2> $OUT/qb_$TAG.err \
  && echo "bench ok" \
  && bash tools/pmc_passes.sh $TAG
