@@ -25,6 +25,7 @@
 
 #include "bls381.h"
 #include "bls381_kernels.hpp"
+#include "bls381_plan.hpp"
 
 using namespace bls381;
 
@@ -163,24 +164,77 @@ int ensure_ws(Ctx* c, size_t bytes) {
   return 0;
 }
 
-// Bump allocator over a workspace (256-byte aligned slices).  Exceeding the
-// capacity throws before anything is launched on the overflowing buffer; ABI
-// entry points map it to an error.
-struct Bump {
-  uint8_t* base;
-  size_t off = 0, cap;
-  explicit Bump(void* b, size_t c = SIZE_MAX) : base((uint8_t*)b), cap(c) {}
-  template <class T> T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    if (count * sizeof(T) > cap || off > cap - count * sizeof(T)) throw std::length_error("workspace bound exceeded");
-    T* p = (T*)(base + off);
-    off += count * sizeof(T);
-    return p;
+// Runs an entry point's body (or a rank's local stage of a collective call); exceptions --
+// a workspace bound exceeded, an allocation -- become error codes.
+template <class F>
+int guarded(F&& f) {
+  try {
+    return f();
+  } catch (const std::exception& e) {
+    t_err = e.what();
+    return BLS381_EARG;
   }
-  size_t left() const { return off < cap ? cap - off : 0; }
+}
+
+// Sizes the context workspace by the caller's own carve: run once over a counting Bump, then,
+// with that many bytes ensured, for real.  The carve only takes slices.
+template <class Carve>
+int carve_ws(Ctx* c, Carve&& carve) {
+  if (int rc = ensure_ws(c, carved_bytes(carve))) return rc;
+  Bump b(c->ws, c->ws_cap);
+  carve(b);
+  return 0;
+}
+
+// The frame of a host-pointer entry point: the context with its lock held, the context
+// workspace carved by the entry, copies in and out on the context stream, one synchronise.
+struct HostCall {
+  Ctx* c;
+  std::unique_lock<std::mutex> lk;
+  hipStream_t s;
+  explicit HostCall(Ctx* ctx) : c(ctx), lk(ctx->mu), s(ctx->stream) {}
+  template <class Carve> int carve(Carve&& cv) { return carve_ws(c, cv); }
+  int upload(void* dst, const void* src, size_t bytes) {
+    if (bytes) HIPC(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  int download(void* dst, const void* src, size_t bytes) {
+    if (bytes) HIPC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    return 0;
+  }
+  int finish() {
+    HIPC(hipStreamSynchronize(s));
+    return 0;
+  }
 };
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-constexpr size_t FPW = 4 * FP_LIMBS;   // bytes per Fp element in SoA buffers
+// returns a failing step's code from the enclosing function
+#define TRY(x)                  \
+  do {                          \
+    int rc__ = (x);             \
+    if (rc__) return rc__;      \
+  } while (0)
+
+// device copies of a host-pointer verify batch (bls381_verify_batch[_randomized]) and the
+// pipeline's own workspace of ws_bytes
+struct VerifyIn {
+  uint8_t *pks, *msgs, *sigs, *doms, *v;
+  void* ws;
+  void carve(Bump& b, size_t n, size_t ws_bytes) {
+    pks = b.take<uint8_t>(48 * n);
+    msgs = b.take<uint8_t>(32 * n);
+    sigs = b.take<uint8_t>(96 * n);
+    doms = b.take<uint8_t>(8 * n);
+    v = b.take<uint8_t>(n);
+    ws = b.take<uint8_t>(ws_bytes);
+  }
+  int upload(HostCall& hc, size_t n, const uint8_t* h_pks, const uint8_t* h_msgs, const uint8_t* h_sigs,
+             const uint8_t* h_doms) {
+    TRY(hc.upload(pks, h_pks, 48 * n));
+    TRY(hc.upload(msgs, h_msgs, 32 * n));
+    TRY(hc.upload(sigs, h_sigs, 96 * n));
+    return hc.upload(doms, h_doms, 8 * n);
+  }
+};
 
 unsigned grid_for(size_t n, int block = KBLOCK) { return (unsigned)((n + block - 1) / block); }
 
@@ -235,11 +289,7 @@ int launch(const char* name, hipStream_t s, dim3 grid, dim3 block, K kern, A... 
   return 0;
 }
 
-#define LAUNCH(name, s, grid, block, kern, ...)                     \
-  do {                                                              \
-    int rc__ = launch(name, s, grid, block, kern, __VA_ARGS__);     \
-    if (rc__) return rc__;                                          \
-  } while (0)
+#define LAUNCH(name, s, grid, block, kern, ...) TRY(launch(name, s, grid, block, kern, __VA_ARGS__))
 
 // final exponentiation + verdict of n Fp12 values (lane-pair SoA): on lane quads while
 // the batch leaves SIMDs idle (k_final_exp_verdict_q: half the per-item latency, more
@@ -252,7 +302,11 @@ int launch(const char* name, hipStream_t s, dim3 grid, dim3 block, K kern, A... 
 #ifndef BLS_FE_OCT_MAX_N
 #define BLS_FE_OCT_MAX_N 8192
 #endif
-int env_knob(const char* name, int def);
+// measurement knobs read once from the environment (the defaults are the shipped layout)
+int env_knob(const char* name, int def) {
+  const char* v = std::getenv(name);
+  return v ? std::atoi(v) : def;
+}
 // BLS381_FE_OCT: 0 = quads (k_final_exp_verdict_q), 2 = octets with the Fp12 products split
 // (k_final_exp_verdict_oq<.., 0>), 3 (default) = the compressed squarings split four ways as well
 // (k_final_exp_verdict_oq<.., 1>).  (1, the squarings split without the products, measured
@@ -266,136 +320,66 @@ bool fe_oct(size_t n) { return fe_oct_mode() && n <= BLS_FE_OCT_MAX_N; }
 // the items whose wave met the compressed squarings' g2 = 0 case; a wave with none exits at once).
 // (r04d measured the throughput FE as six launches with HBM intermediates, BLS_FE_SPLIT: 9.99 ms
 // per 2^16 against ~9.1 in one kernel; removed in r06)
-int launch_final_exp(hipStream_t s, size_t n, const uint32_t* f, const uint8_t* st, uint8_t* verdicts) {
+// vpi: Fp12 values per item (2: the octet Miller path of small verify batches wrote one value per
+// pair, and the latency kernels multiply them first; such batches never reach the throughput form)
+static_assert(BLS_ML_OCT_MAX_N <= BLS_FE_QUAD_MAX_N, "two values per item only on the latency kernels");
+int launch_final_exp(hipStream_t s, size_t n, const uint32_t* f, const uint8_t* st, uint8_t* verdicts, int vpi = 1) {
+  const dim3 b(KBLOCK);
+  const bool two = vpi == 2;
   if (fe_oct(n) && fe_oct_mode() == 3)
-    LAUNCH("final_exp_oo", s, dim3(grid_for(8 * n)), dim3(KBLOCK), (k_final_exp_verdict_oq<1, 1>), n, f, st, verdicts);
+    LAUNCH("final_exp_oo", s, dim3(grid_for(8 * n)), b, (two ? k_final_exp_verdict_oq<2, 1> : k_final_exp_verdict_oq<1, 1>),
+           n, f, st, verdicts);
   else if (fe_oct(n) && fe_oct_mode() == 2)
-    LAUNCH("final_exp_oq", s, dim3(grid_for(8 * n)), dim3(KBLOCK), k_final_exp_verdict_oq<1>, n, f, st, verdicts);
-  else if (n <= BLS_FE_QUAD_MAX_N)
-    LAUNCH("final_exp_q", s, dim3(grid_for(4 * n)), dim3(KBLOCK), k_final_exp_verdict_q<1>, n, f, st, verdicts);
+    LAUNCH("final_exp_oq", s, dim3(grid_for(8 * n)), b, (two ? k_final_exp_verdict_oq<2> : k_final_exp_verdict_oq<1>), n, f,
+           st, verdicts);
+  else if (two || n <= BLS_FE_QUAD_MAX_N)
+    LAUNCH("final_exp_q", s, dim3(grid_for(4 * n)), b, (two ? k_final_exp_verdict_q<2> : k_final_exp_verdict_q<1>), n, f, st,
+           verdicts);
   else {
-    LAUNCH("final_exp", s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_final_exp_verdict, n, f, st, verdicts);
-    LAUNCH("final_exp_redo", s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_final_exp_redo, n, f, verdicts);
+    LAUNCH("final_exp", s, dim3(grid_for(2 * n)), b, k_final_exp_verdict, n, f, st, verdicts);
+    LAUNCH("final_exp_redo", s, dim3(grid_for(2 * n)), b, k_final_exp_redo, n, f, verdicts);
   }
   return 0;
 }
-#define LAUNCH_FE(s, n, f, st, v)                                                                   \
-  do {                                                                                              \
-    int rc__ = launch_final_exp(s, n, (const uint32_t*)(f), (const uint8_t*)(st), v);               \
-    if (rc__) return rc__;                                                                          \
-  } while (0)
+#define LAUNCH_FE(s, n, f, st, v) TRY(launch_final_exp(s, n, (const uint32_t*)(f), (const uint8_t*)(st), v))
 
 // ----------------------------------------------------- verify_batch (C2) --
-struct VerifyWs {
-  uint32_t *pk_aff, *sig_aff, *h_aff, *f, *koff, *ml_L;
-  uint8_t *pk_st, *sig_st, *f_st, *ml_st;
-};
-// bls_verify batches of at most this many items run each Miller pair on its own lane
-// quad (k_miller_verify_o, 8 lanes per item: the lowest latency), up to
-// BLS_ML_QUAD_MAX_N both pairs of an item on one quad (k_miller_verify_q), above that
-// on lane pairs (k_miller_verify: the least work per item)
-#ifndef BLS_ML_OCT_MAX_N
-#define BLS_ML_OCT_MAX_N 8192
-#endif
+// (VerifyWs, its carve and the Miller-stage thresholds: bls381_plan.hpp)
 // hash_to_G2 of batches of at most this many messages runs the wide candidate search first
 // (k_hash_search: 16 lanes per message, one Legendre symbol each)
 #ifndef BLS_HASH_WIDE_MAX_N
 #define BLS_HASH_WIDE_MAX_N 8192
 #endif
-// Fp12 values the Miller stage of a verify batch writes (two per item on the octet path)
-size_t verify_nf(size_t n) { return n <= BLS_ML_OCT_MAX_N ? 2 * n : n; }
-// the split Miller loop (k_ml_lines -> k_ml_accum) of the throughput path runs in chunks of at
-// most this many items; its line products take ML_L_WORDS_PER_ITEM words per item of a chunk
-#ifndef BLS_ML_SPLIT
-#define BLS_ML_SPLIT 1
+// with the search offsets known, up to this many messages the cofactor map runs on lane octets or
+// quads (k_hash_g2_o / k_hash_g2_q, its independent products two at a time), above on lane pairs
+#ifndef BLS_HASH_QUAD_MAX_N
+#define BLS_HASH_QUAD_MAX_N 8192
 #endif
-#ifndef BLS_ML_SPLIT_CHUNK
-#define BLS_ML_SPLIT_CHUNK 65536
-#endif
-bool verify_split(size_t n);
-size_t verify_split_chunk(size_t n) { return verify_split(n) ? std::min<size_t>(n, BLS_ML_SPLIT_CHUNK) : 0; }
-// lines = false: a workspace for the decodes and the hash only (no split-loop line buffer;
-// the randomized path's own decode/hash workspace, whose pairings run elsewhere)
-size_t verify_ws_size(size_t n, bool lines = true) {
-  const size_t ch = lines ? verify_split_chunk(n) : 0;
-  return align256(2 * FPW * n) + align256(4 * FPW * n) * 2 + align256(12 * FPW * verify_nf(n)) + 2 * align256(n) +
-         align256(verify_nf(n)) + align256(4 * n) + align256(4 * ML_L_WORDS_PER_ITEM * ch) + align256(ch) + 1024;
-}
-VerifyWs carve_verify(void* ws, size_t n, bool lines = true) {
-  Bump b(ws);
-  VerifyWs w;
-  const size_t ch = lines ? verify_split_chunk(n) : 0;
-  w.ml_L = ch ? b.take<uint32_t>(ML_L_WORDS_PER_ITEM * ch) : nullptr;
-  w.ml_st = ch ? b.take<uint8_t>(ch) : nullptr;
-  w.pk_aff = b.take<uint32_t>(2 * FP_LIMBS * n);
-  w.sig_aff = b.take<uint32_t>(4 * FP_LIMBS * n);
-  w.h_aff = b.take<uint32_t>(4 * FP_LIMBS * n);
-  w.f = b.take<uint32_t>(12 * FP_LIMBS * verify_nf(n));
-  w.pk_st = b.take<uint8_t>(n);
-  w.sig_st = b.take<uint8_t>(n);
-  w.f_st = b.take<uint8_t>(verify_nf(n));
-  w.koff = b.take<uint32_t>(n);
-  return w;
-}
-
-// 1: decode_g2 runs on the side stream after decode_g1 (r01k: 1.59-1.61 M ->
-// 1.62 M verifications/s on one box); 0: on the main stream before hash_to_g2
-// bls_verify batches of at most this many items run their Miller loops on lane quads
-// (k_miller_verify_q), larger ones on lane pairs (k_miller_verify: 13% less work per item).
-// Below ~2^16 items the pair kernels leave SIMDs with one latency-bound wave, so the quads
-// win: r02t, wall ms pair -> quad at 16,385 / 32,768 / 49,152 items: 28.7 -> 18.7 / 20.7 /
-// 27.7; at 65,536 the pairs win (32.4 vs 35.2).  BLS_FE_QUAD_MAX_N follows the same curve.
-#ifndef BLS_ML_QUAD_MAX_N
-#define BLS_ML_QUAD_MAX_N 49152
-#endif
-bool verify_split(size_t n) { return BLS_ML_SPLIT && n > BLS_ML_QUAD_MAX_N; }
-
-#ifndef BLS_DECODE_G2_SIDE
-#define BLS_DECODE_G2_SIDE 1
-#endif
-// A/B knobs read once from the environment (measurement only; defaults are the shipped
-// layout): BLS381_G2_ONE_LANE bit 0 = decode_g2 on one lane per item.  Default 1 (r03k, same
-// box, two runs each): the one-lane decode_g2 beside hash_to_G2 runs 4.1 -> 3.45 ms, C2 2.116 ->
-// 2.133-2.139 M/s.  (Bit 1, the whole hash_to_g2 on one lane, spilled -- 10 ms against 6.6 --
-// and was removed in r06.)
-int env_knob(const char* name, int def) {
-  const char* v = std::getenv(name);
-  return v ? std::atoi(v) : def;
-}
-int g2_one_lane() {
-  static const int v = env_knob("BLS381_G2_ONE_LANE", 1);
-  return v;
-}
-// hash_to_G2 of throughput batches as k_hash_cand_1 (search + root, one lane per item) then
-// k_hash_bp (cofactor map, lane pairs); BLS381_HASH_SPLIT=0: the one pair kernel k_hash_g2
-int hash_split() {
-  static const int v = env_knob("BLS381_HASH_SPLIT", 1);
+// BLS381_ML_OCTET (default 1): the latency Miller loops run one octet per Miller pair
+// (k_miller_verify_oo, k_miller_tasks<8>: 10 product steps per doubling iteration against 19 on a
+// quad); 0 = one quad per pair (k_miller_verify_o, k_miller_tasks<4>)
+int ml_octet() {
+  static const int v = env_knob("BLS381_ML_OCTET", 1);
   return v;
 }
 // hash_to_G2 of n messages (throughput form, no precomputed search offsets) into h_aff, status
-// into st (may be null); prio as k_hash_g2's
+// into st (may be null): k_hash_cand_1 (search + root, one lane per item), then k_hash_bp (cofactor
+// map, lane pairs)
 int launch_hash_g2(hipStream_t s, size_t n, const uint8_t* msgs, uint32_t mlen, const uint8_t* doms, int dom_stride,
-                   uint32_t* h_aff, uint8_t* st, int prio = 0) {
-  if (hash_split() && !prio) {
-    LAUNCH("hash_cand", s, dim3(grid_for(n)), dim3(KBLOCK), k_hash_cand_1, n, msgs, mlen, doms, dom_stride, h_aff);
-    LAUNCH("hash_bp", s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_hash_bp, n, h_aff, st);
-    return 0;
-  }
-  LAUNCH("hash_to_g2", s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_hash_g2, n, msgs, mlen, doms, dom_stride, h_aff, st,
-         (const uint32_t*)nullptr, prio);
+                   uint32_t* h_aff, uint8_t* st) {
+  LAUNCH("hash_cand", s, dim3(grid_for(n)), dim3(KBLOCK), k_hash_cand_1, n, msgs, mlen, doms, dom_stride, h_aff);
+  LAUNCH("hash_bp", s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_hash_bp, n, h_aff, st);
   return 0;
 }
 // hash_to_G2 with the search offsets known (koff from k_hash_search, or nullptr): the latency
-// batches.  BLS381_HASH_QUAD_MAX_N (default 8192, 0 = off): up to that many messages the cofactor
-// map runs on lane quads (k_hash_g2_q), its independent products two at a time.
+// batches.  BLS381_HASH_OCT (default 1): the doublings on octets (k_hash_g2_o), 0 = on quads.
 int launch_hash_koff(hipStream_t s, size_t n, const uint8_t* msgs, uint32_t mlen, const uint8_t* doms, int dom_stride,
                      uint32_t* h_aff, uint8_t* st, const uint32_t* koff, int prio) {
-  static const size_t quad_max = (size_t)env_knob("BLS381_HASH_QUAD_MAX_N", 8192);
-  static const int oct = env_knob("BLS381_HASH_OCT", 1);   // the doublings on octets (k_hash_g2_o)
-  if (n <= quad_max && oct)
+  static const int oct = env_knob("BLS381_HASH_OCT", 1);
+  if (n <= BLS_HASH_QUAD_MAX_N && oct)
     LAUNCH("hash_to_g2_o", s, dim3(grid_for(8 * n)), dim3(KBLOCK), k_hash_g2_o, n, msgs, mlen, doms, dom_stride, h_aff,
            st, koff, prio);
-  else if (n <= quad_max)
+  else if (n <= BLS_HASH_QUAD_MAX_N)
     LAUNCH("hash_to_g2_q", s, dim3(grid_for(4 * n)), dim3(KBLOCK), k_hash_g2_q, n, msgs, mlen, doms, dom_stride, h_aff,
            st, koff, prio);
   else
@@ -403,99 +387,60 @@ int launch_hash_koff(hipStream_t s, size_t n, const uint8_t* msgs, uint32_t mlen
            st, koff, prio);
   return 0;
 }
-#define LAUNCH_HASH(...)                        \
-  do {                                          \
-    int rc__ = launch_hash_g2(__VA_ARGS__);     \
-    if (rc__) return rc__;                      \
-  } while (0)
 
 int run_verify_pairings(size_t n, const VerifyWs& w, uint8_t* verdicts, hipStream_t s, bool sig_in_loop);
 
+// Decodes and hash_to_G2 of a verify batch, then its pairings.  Three schedules (measured in
+// DESIGN.md §10): the one-lane stages (hash search + root, decode_g1, decode_g2) share the chip,
+// the full-chip cofactor map runs alone.
 int run_verify_batch(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* msgs, const uint8_t* sigs,
                      const uint8_t* doms, uint8_t* verdicts, void* ws, hipStream_t s) {
   VerifyWs w = carve_verify(ws, n);
   const dim3 g(grid_for(n)), g2(grid_for(2 * n)), b(KBLOCK);   // G1: lane per item; G2/Fp12: lane pair
   const int chk = check_subgroups();
   // throughput path under the strict policy: the signature's G2 test moves from decode_g2 into
-  // the Miller loop, which computes [|x|] sig anyway (k_miller_verify's sig_check)
+  // the Miller loop, which computes [|x|] sig anyway (k_ml_lines' sig_check)
   const bool sig_in_loop = chk && n > BLS_ML_QUAD_MAX_N;
+  const int pk_flags = policy_flags(chk), sig_flags = policy_flags(sig_in_loop ? 0 : chk);
+  const bool wide = n <= BLS_HASH_WIDE_MAX_N;
   std::lock_guard<std::mutex> lk(c->fork_mu);
-  // decode_g1 (one lane per item: one wave per SIMD) and, by default, decode_g2
-  // on the side stream, beside hash_to_g2; the Miller loop waits for both branches.
-  // Decode waves fill the SIMD slots that finished hash waves free (measured in DESIGN.md §10).
-  // BLS381_C2_ORDER (measurement knob): 1 = the decodes on the side stream beside hash_to_G2,
-  // 0 = everything in sequence on the main stream
-  // 2 = as 1 with decode_g2 before decode_g1; 3 (default) = as 1, and the split hash's
-  // cofactor launch (k_hash_bp) waits for both decodes instead of sharing the chip with
-  // them: the one-lane search + root (k_hash_cand_1) pairs with the one-lane decodes, the
-  // full-chip k_hash_bp then runs alone.  r03v, one box, two runs each: order 1 2.137 /
-  // 2.152 M/s (k_hash_bp 4.9-5.0 ms beside decode_g2), order 3 2.199 / 2.201 (3.4 ms).
-  // Under the strict policy decode_g1 carries the G1 subgroup test (3.6 ms), and waiting for
-  // it costs more than sharing the chip: order 1 2.111 / 2.113 against order 3 2.062 / 2.051
-  // (r03y).
-  // 4 = as 3 with decode_g2 on a second side stream, so the three one-lane launches (search +
-  // root, decode_g1, decode_g2) share the chip at once and hash_bp waits for all three: the
-  // prologue is max(2.4, 2.8, 2.3) + 3.4 ms instead of max(1.7 + 1.6, 2.2) + 3.4.  r04h, one
-  // box, four alternating pairs of 10 steps: order 3 2.151-2.191 M/s (mean 2.174), order 4
-  // 2.211-2.246 (mean 2.228), every pair won by 4.  Strict, three pairs: order 1 2.131-2.140,
-  // order 4 2.122-2.125, order 3 2.026-2.038 (decode_g1's 4 ms G1 test is the critical path).
-  // Default: 4 for py_ecc, 1 for strict.
-  static const int c2_order_env = env_knob("BLS381_C2_ORDER", -1);
-  const int c2_order = c2_order_env >= 0 ? c2_order_env : (chk ? 1 : 4);
-  // order 4's three one-lane launches as ONE launch whose workgroups take the three roles in dispatch
-  // order, the hash search first (k_prologue_1, r06): as three streams the SIMD slots went to whichever
-  // stream's waves the dispatcher took first, and the prologue took 2.8-2.9 or 3.2-3.7 ms from step to
-  // step (profiles/prologue_spans_r06c.txt); fused 2.9-3.0 on a box where the three streams ran 0.9-1.9 %
-  // slower per step (profiles/bench_r06e_*.json, alternating)
-  if (c2_order == 4 && n > BLS_HASH_WIDE_MAX_N && hash_split() && (g2_one_lane() & 1)) {
+  if (!chk && !wide) {
+    // py_ecc, throughput: the three one-lane stages as ONE launch whose workgroups take the three
+    // roles in dispatch order, the hash search first (k_prologue_1); then the cofactor map
     LAUNCH("prologue", s, dim3(3 * grid_for(n)), b, k_prologue_1<0>, n, pks, sigs, msgs, (uint32_t)32, doms, 8,
            (const uint8_t*)nullptr, w.pk_aff, w.pk_st, w.sig_aff, w.sig_st, w.h_aff, (uint32_t*)nullptr,
-           (uint8_t*)nullptr, policy_flags(chk), policy_flags(sig_in_loop ? 0 : chk));
+           (uint8_t*)nullptr, pk_flags, sig_flags);
     LAUNCH("hash_bp", s, g2, b, k_hash_bp, n, w.h_aff, (uint8_t*)nullptr);
     return run_verify_pairings(n, w, verdicts, s, sig_in_loop);
   }
-  hipStream_t sd = c2_order ? c->side : s;
   HIPC(hipEventRecord(c->ev_fork, s));
   HIPC(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-  if (c2_order != 2) LAUNCH("decode_g1", sd, g, b, k_decode_g1, n, pks, w.pk_aff, w.pk_st, policy_flags(chk));
-#if BLS_DECODE_G2_SIDE
-  // both decodes in sequence beside hash_to_G2 (order 4: decode_g2 on its own side stream)
-  if (c2_order == 4 && (g2_one_lane() & 1)) {
+  LAUNCH("decode_g1", c->side, g, b, k_decode_g1, n, pks, w.pk_aff, w.pk_st, pk_flags);
+  if (!chk) {
+    // py_ecc, small batches: decode_g2 on a second side stream, and the wide search first (16
+    // candidates per message in one round), so the hash does not wait for the batch's slowest
+    // sequential search
     HIPC(hipStreamWaitEvent(c->side2, c->ev_fork, 0));
-    LAUNCH("decode_g2_1", c->side2, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st,
-           policy_flags(sig_in_loop ? 0 : chk));
+    LAUNCH("decode_g2_1", c->side2, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st, sig_flags);
     HIPC(hipEventRecord(c->ev_join2, c->side2));
-  } else if (g2_one_lane() & 1)
-    LAUNCH("decode_g2_1", sd, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st, policy_flags(sig_in_loop ? 0 : chk));
-  else
-    LAUNCH("decode_g2", sd, g2, b, k_decode_g2, n, sigs, w.sig_aff, w.sig_st, policy_flags(sig_in_loop ? 0 : chk));
-  if (c2_order == 2) LAUNCH("decode_g1", sd, g, b, k_decode_g1, n, pks, w.pk_aff, w.pk_st, policy_flags(chk));
-  HIPC(hipEventRecord(c->ev_join, c->side));
-#else
-  // order 2 skipped decode_g1 above (it runs after decode_g2 on the side stream when that
-  // is built in); here decode_g2 is on the main stream, so decode_g1 goes first on the side
-  if (c2_order == 2) LAUNCH("decode_g1", sd, g, b, k_decode_g1, n, pks, w.pk_aff, w.pk_st, policy_flags(chk));
-  HIPC(hipEventRecord(c->ev_join, c->side));
-  LAUNCH("decode_g2", s, g2, b, k_decode_g2, n, sigs, w.sig_aff, w.sig_st, policy_flags(sig_in_loop ? 0 : chk));
-#endif
-  // small batches: the wide search first (16 candidates per message in one round), so the
-  // hash does not wait for the batch's slowest sequential search
-  const bool wide = n <= BLS_HASH_WIDE_MAX_N;
-  if (wide)
+    HIPC(hipEventRecord(c->ev_join, c->side));
     LAUNCH("hash_search", s, dim3(grid_for(16 * n)), b, k_hash_search<16>, n, msgs, (uint32_t)32, doms, 8, w.koff);
-  if (!wide && (c2_order == 3 || c2_order == 4) && hash_split()) {
-    LAUNCH("hash_cand", s, g, b, k_hash_cand_1, n, msgs, (uint32_t)32, doms, 8, w.h_aff);
+    TRY(launch_hash_koff(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr, (const uint32_t*)w.koff, 0));
     HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
-    if (c2_order == 4 && (g2_one_lane() & 1)) HIPC(hipStreamWaitEvent(s, c->ev_join2, 0));
-    LAUNCH("hash_bp", s, g2, b, k_hash_bp, n, w.h_aff, (uint8_t*)nullptr);
-  } else if (!wide)
-    LAUNCH_HASH(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr);
-  else if (int rc_h = launch_hash_koff(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr, (const uint32_t*)w.koff, 0))
-    return rc_h;
+    HIPC(hipStreamWaitEvent(s, c->ev_join2, 0));
+    return run_verify_pairings(n, w, verdicts, s, sig_in_loop);
+  }
+  // strict: both decodes in sequence on the side stream beside hash_to_G2 (decode_g1 carries the G1
+  // subgroup test, and waiting for it before the cofactor map costs more than sharing the chip)
+  LAUNCH("decode_g2_1", c->side, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st, sig_flags);
+  HIPC(hipEventRecord(c->ev_join, c->side));
+  if (wide) {
+    LAUNCH("hash_search", s, dim3(grid_for(16 * n)), b, k_hash_search<16>, n, msgs, (uint32_t)32, doms, 8, w.koff);
+    TRY(launch_hash_koff(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr, (const uint32_t*)w.koff, 0));
+  } else {
+    TRY(launch_hash_g2(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr));
+  }
   HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
-#if BLS_DECODE_G2_SIDE
-  if (c2_order == 4 && (g2_one_lane() & 1)) HIPC(hipStreamWaitEvent(s, c->ev_join2, 0));
-#endif
   return run_verify_pairings(n, w, verdicts, s, sig_in_loop);
 }
 
@@ -503,13 +448,10 @@ int run_verify_batch(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* msgs, 
 // the decoded points in `w` (statuses pk_st / sig_st, hash points h_aff), verdicts out.
 // sig_in_loop: the strict policy's G2 test of the signatures is still to be done (in the loop).
 int run_verify_pairings(size_t n, const VerifyWs& w, uint8_t* verdicts, hipStream_t s, bool sig_in_loop) {
-  const dim3 g2(grid_for(2 * n)), b(KBLOCK);
+  const dim3 b(KBLOCK);
   if (n <= BLS_ML_OCT_MAX_N) {
-    // lowest latency: one quad per Miller pair; the FE multiplies the two values of each item
-    // BLS381_ML_OCTET (default 1): one octet per Miller pair (k_miller_verify_oo, 10 product steps
-    // per doubling iteration against 19 on a quad); 0 = one quad per pair (k_miller_verify_o)
-    static const int ml_octet = env_knob("BLS381_ML_OCTET", 1);
-    if (ml_octet)
+    // lowest latency: one octet (or quad) per Miller pair; the FE multiplies the two values of each item
+    if (ml_octet())
       LAUNCH("miller_loop_2oo", s, dim3(grid_for(16 * n)), b, k_miller_verify_oo, n, (const uint32_t*)w.sig_aff,
              (const uint8_t*)w.sig_st, (const uint32_t*)w.pk_aff, (const uint8_t*)w.pk_st, (const uint32_t*)w.h_aff,
              w.f, w.f_st);
@@ -517,16 +459,7 @@ int run_verify_pairings(size_t n, const VerifyWs& w, uint8_t* verdicts, hipStrea
       LAUNCH("miller_loop_2o", s, dim3(grid_for(8 * n)), b, k_miller_verify_o, n, (const uint32_t*)w.sig_aff,
              (const uint8_t*)w.sig_st, (const uint32_t*)w.pk_aff, (const uint8_t*)w.pk_st, (const uint32_t*)w.h_aff,
              w.f, w.f_st);
-    if (fe_oct(n) && fe_oct_mode() == 3)
-      LAUNCH("final_exp_oo", s, dim3(grid_for(8 * n)), b, (k_final_exp_verdict_oq<2, 1>), n, (const uint32_t*)w.f,
-             (const uint8_t*)w.f_st, verdicts);
-    else if (fe_oct(n) && fe_oct_mode() == 2)
-      LAUNCH("final_exp_oq", s, dim3(grid_for(8 * n)), b, k_final_exp_verdict_oq<2>, n, (const uint32_t*)w.f,
-             (const uint8_t*)w.f_st, verdicts);
-    else
-      LAUNCH("final_exp_q", s, dim3(grid_for(4 * n)), b, k_final_exp_verdict_q<2>, n, (const uint32_t*)w.f,
-             (const uint8_t*)w.f_st, verdicts);
-    return 0;
+    return launch_final_exp(s, n, w.f, w.f_st, verdicts, 2);
   }
   if (n <= BLS_ML_QUAD_MAX_N) {
     // latency path: one item per lane quad, its two pairs side by side (half the per-item latency,
@@ -534,7 +467,7 @@ int run_verify_pairings(size_t n, const VerifyWs& w, uint8_t* verdicts, hipStrea
     LAUNCH("miller_loop_2q", s, dim3(grid_for(4 * n)), b, k_miller_verify_q, n, (const uint32_t*)w.sig_aff,
            (const uint8_t*)w.sig_st, (const uint32_t*)w.pk_aff, (const uint8_t*)w.pk_st, (const uint32_t*)w.h_aff,
            w.f, w.f_st);
-  } else if (verify_split(n)) {
+  } else {
     // the split Miller loop, in chunks: running points and line products on quads, then the
     // f accumulation on lane pairs
     const size_t ch = verify_split_chunk(n);
@@ -555,67 +488,12 @@ int run_verify_pairings(size_t n, const VerifyWs& w, uint8_t* verdicts, hipStrea
       LAUNCH("miller_accum", s, dim3(grid_for(2 * cnt)), b, k_ml_accum, n, i0, cnt, (const uint32_t*)w.ml_L,
              (const uint8_t*)w.ml_st, w.f, w.f_st, (size_t)0);
     }
-  } else {
-    LAUNCH("miller_loop_2", s, g2, b, k_miller_verify, n, (const uint32_t*)w.sig_aff, (const uint8_t*)w.sig_st,
-           (const uint32_t*)w.pk_aff, (const uint8_t*)w.pk_st, (const uint32_t*)w.h_aff, w.f, w.f_st,
-           sig_in_loop ? 1 : 0);
   }
-  if (int rc = launch_final_exp(s, n, (const uint32_t*)w.f, (const uint8_t*)w.f_st, verdicts)) return rc;
-  return 0;
+  return launch_final_exp(s, n, w.f, w.f_st, verdicts);
 }
 
 // --------------------------------------------------------- aggregation --
-// plan chunk levels for groups given by host offsets
-struct AggPlan {
-  std::vector<std::vector<agg_chunk>> levels;   // chunks per level
-};
-// Level-1 chunks hold 1-4 rounds of one input per lane slot (KBLOCK / lanes-per-point inputs per
-// round): as few rounds as still give AGG_WG_TARGET workgroups (two waves per SIMD over the whole
-// chip), so a large single group (C4: 2^17 keys) is not summed four keys per lane on half the SIMDs.
-// CHUNK_MIN bounds the chunk count for the workspace sizes (G2 points: 64 per round).
-constexpr uint32_t CHUNK_MIN = KBLOCK / 2;
-constexpr size_t AGG_WG_TARGET = 1024;
-// level-1 chunks averaging fewer inputs than this are summed one lane per chunk (k_agg_lanes)
-constexpr size_t AGG_LANE_AVG_MAX = 8;
-constexpr uint32_t CHUNK_LN = 4 * KBLOCK;
-
-AggPlan plan_agg(size_t ng, const uint32_t* offsets, int lanes_per_point = 1) {
-  AggPlan p;
-  std::vector<uint32_t> cur_off(offsets, offsets + ng + 1);
-  const uint32_t per_round = KBLOCK / (uint32_t)lanes_per_point;
-  const size_t total = ng ? (size_t)offsets[ng] - offsets[0] : 0;
-  const size_t rounds = std::min<size_t>(4, std::max<size_t>(1, (total + AGG_WG_TARGET * per_round - 1) /
-                                                                     (AGG_WG_TARGET * per_round)));
-  uint32_t chunk = per_round * (uint32_t)rounds;
-  bool first = true;
-  while (true) {
-    std::vector<agg_chunk> lv;
-    std::vector<uint32_t> next_off(ng + 1, 0);
-    bool multi = false;
-    for (size_t g = 0; g < ng; ++g) {
-      next_off[g] = (uint32_t)lv.size();
-      const uint32_t b0 = cur_off[g], e0 = cur_off[g + 1];
-      if (e0 <= b0) { lv.push_back({b0, b0}); continue; }
-      uint32_t cnt = 0;
-      for (uint32_t x = b0; x < e0; x += chunk) { lv.push_back({x, x + chunk < e0 ? x + chunk : e0}); ++cnt; }
-      if (cnt > 1) multi = true;
-    }
-    next_off[ng] = (uint32_t)lv.size();
-    p.levels.push_back(lv);
-    if (!multi && !first) break;
-    if (!multi) break;
-    cur_off = next_off;
-    chunk = CHUNK_LN;
-    first = false;
-  }
-  return p;
-}
-
-size_t agg_ws_size(const AggPlan& p, int ncomp) {
-  size_t s = 1024;
-  for (auto& lv : p.levels) s += align256(lv.size() * sizeof(agg_chunk)) + align256(lv.size() * ncomp * FPW) + align256(lv.size());
-  return s;
-}
+// (the chunk plan, AggPlan / plan_agg, and its workspace size: bls381_plan.hpp)
 
 // runs the plan; returns device pointers to the final per-group Jacobian sums / bad flags.
 // Level 0 decodes compressed points (d_in), reads registry entries (reg), or -- with
@@ -666,272 +544,8 @@ int run_agg(const AggPlan& p, size_t ng, const uint8_t* d_in, void* ws, hipStrea
 }
 
 // ------------------------------------------------- verify_multiple pieces --
-// Host plan for a batch of bls_verify_multiple calls.  Within each call the
-// pubkeys are grouped by distinct message (first-appearance order), as py_ecc's
-// verify_multiple does; every group becomes one pair
-// (hash_to_G2(m), sum of its pubkeys) and each call adds (sig, -g1).  When the
-// key bytes are on the host, a group whose keys are all the canonical infinity
-// encoding and an infinite signature are dropped (py_ecc's pairing with an
-// infinite point is 1).  A call's pairs run two at a time on lane quads
-// (k_miller_quads: one pair per half, shared squarings); a call with several
-// quads multiplies them in segmented product passes; one final exponentiation
-// per call.
-constexpr int32_t PAIR_NONE = INT32_MIN;
-
-// verify_multiple batches of at most this many Miller pairs run one pair per lane quad
-// (the latency path of small batches: an epoch's attestations, single calls)
-#ifndef BLS_VM_TASK_MAX
-#define BLS_VM_TASK_MAX 8192
-#endif
-struct VmPlan {
-  size_t n_calls = 0, n_keys = 0, G = 0, nquads = 0;
-  std::vector<uint32_t> key_idx;        // caller key index of every group member, in group order
-  std::vector<uint32_t> group_off;      // G + 1 offsets into key_idx
-  std::vector<uint8_t> group_msg;       // G x mlen
-  std::vector<uint32_t> group_call;     // G: owning call (whose domain hashes the message)
-  std::vector<int32_t> quad_pair;       // 2 per quad: group >= 0, -(call + 1) = the signature pair, or PAIR_NONE
-  std::vector<uint32_t> call_quad_off;  // n_calls + 1 offsets into the quads
-  std::vector<std::vector<agg_chunk>> passes;  // segmented Fp12 products (empty: one quad per call)
-  // latency path (small batches): one quad per Miller pair (k_miller_tasks_q1); the pair
-  // tasks are the quad_pair entries, and these passes multiply them per call
-  bool tasks = false;
-  std::vector<std::vector<agg_chunk>> task_passes;
-  // large batches: the signature pairs leave the quads (each call's group pairs fill whole
-  // quads; its signature pair runs on a side stream beside hash_to_G2).  Miller values sit
-  // in per-call slot ranges [quads of call c][signature of call c]: quad q writes slot
-  // quad_slot[q], call c's signature slot sig_slot[c] (task sig_task[c]); passes multiply them.
-  std::vector<uint32_t> quad_slot, sig_slot;
-  std::vector<int32_t> sig_task;
-  size_t nslots = 0;
-  AggPlan agg;                                 // group pubkey sums over key_idx order
-};
-
-constexpr uint32_t PROD_CHUNK = 8;
-
-// Segmented product passes over segments off[c]..off[c+1]: each pass multiplies
-// runs of <= PROD_CHUNK values; it ends when every segment is one value.  An
-// empty segment yields one chunk {b, b} (product 1).  At least one pass runs.
-std::vector<std::vector<agg_chunk>> plan_products(std::vector<uint32_t> off) {
-  std::vector<std::vector<agg_chunk>> passes;
-  const size_t ns = off.size() - 1;
-  while (true) {
-    std::vector<agg_chunk> chunks;
-    std::vector<uint32_t> next(ns + 1, 0);
-    bool more = false;
-    for (size_t c = 0; c < ns; ++c) {
-      next[c] = (uint32_t)chunks.size();
-      const uint32_t b0 = off[c], e0 = off[c + 1];
-      if (e0 <= b0) { chunks.push_back({b0, b0}); continue; }
-      for (uint32_t x = b0; x < e0; x += PROD_CHUNK) chunks.push_back({x, x + PROD_CHUNK < e0 ? x + PROD_CHUNK : e0});
-      if (e0 - b0 > PROD_CHUNK) more = true;
-    }
-    next[ns] = (uint32_t)chunks.size();
-    passes.push_back(std::move(chunks));
-    off = std::move(next);
-    if (!more) break;
-  }
-  return passes;
-}
-
-bool is_inf_encoding(const uint8_t* b, size_t len) {
-  if (b[0] != 0xC0) return false;
-  for (size_t i = 1; i < len; ++i)
-    if (b[i]) return false;
-  return true;
-}
-
-// h_pks / h_sigs may be NULL (device-resident keys / signatures: nothing is dropped)
-// 64-bit mix of a message (8-byte words, multiply-xorshift), for the grouping table
-uint64_t msg_hash(const uint8_t* m, size_t len) {
-  uint64_t h = 0x9e3779b97f4a7c15ull ^ len;
-  size_t i = 0;
-  for (; i + 8 <= len; i += 8) {
-    uint64_t w;
-    std::memcpy(&w, m + i, 8);
-    h = (h ^ w) * 0xbf58476d1ce4e5b9ull;
-    h ^= h >> 31;
-  }
-  uint64_t t = 0;
-  for (size_t k = 0; i + k < len; ++k) t |= (uint64_t)m[i + k] << (8 * k);
-  h = (h ^ t) * 0x94d049bb133111ebull;
-  return h ^ (h >> 29);
-}
-
-// Shared tail of the planners: small batches run every pair (signatures included) as a
-// lane-quad task; large ones take the signature pairs out of the quads (VmPlan comments).
-void finish_plan(VmPlan& pl) {
-  const size_t n_calls = pl.n_calls;
-  pl.nquads = pl.quad_pair.size() / 2;
-  pl.tasks = 2 * pl.nquads <= BLS_VM_TASK_MAX;
-  if (pl.tasks) {
-    std::vector<uint32_t> toff(pl.call_quad_off.size());
-    for (size_t k = 0; k < toff.size(); ++k) toff[k] = 2 * pl.call_quad_off[k];
-    pl.task_passes = plan_products(toff);
-    return;
-  }
-  std::vector<int32_t> qp;
-  std::vector<uint32_t> cqo{0}, foff{0};
-  pl.sig_task.assign(n_calls, PAIR_NONE);
-  std::vector<int32_t> groups;
-  for (size_t c = 0; c < n_calls; ++c) {
-    groups.clear();
-    for (uint32_t e = 2 * pl.call_quad_off[c]; e < 2 * pl.call_quad_off[c + 1]; ++e) {
-      const int32_t v = pl.quad_pair[e];
-      if (v >= 0) groups.push_back(v);
-      else if (v != PAIR_NONE) pl.sig_task[c] = v;
-    }
-    for (size_t k = 0; k < groups.size(); k += 2) {
-      qp.push_back(groups[k]);
-      qp.push_back(k + 1 < groups.size() ? groups[k + 1] : PAIR_NONE);
-    }
-    cqo.push_back((uint32_t)(qp.size() / 2));
-    foff.push_back(cqo.back() + (uint32_t)(c + 1));
-  }
-  pl.quad_pair = std::move(qp);
-  pl.call_quad_off = std::move(cqo);
-  pl.nquads = pl.quad_pair.size() / 2;
-  pl.nslots = pl.nquads + n_calls;
-  pl.quad_slot.resize(pl.nquads);
-  pl.sig_slot.resize(n_calls);
-  for (size_t c = 0; c < n_calls; ++c) {
-    for (uint32_t q = pl.call_quad_off[c]; q < pl.call_quad_off[c + 1]; ++q) pl.quad_slot[q] = q + (uint32_t)c;
-    pl.sig_slot[c] = foff[c + 1] - 1;
-  }
-  pl.passes = plan_products(foff);
-}
-
-// Host plan of a verify_multiple batch: per call, pubkeys grouped by distinct message
-// (py_ecc's verify_multiple: groups in first-occurrence order, members in index order).
-// One flat open-addressing table (generation-stamped, reused across calls) and a
-// counting sort per call: linear in the number of keys.
-VmPlan plan_vm(size_t n_calls, const uint32_t* call_off, const uint8_t* msgs, size_t mlen, const uint8_t* h_pks,
-               const uint8_t* h_sigs, const int* with_sig) {
-  VmPlan pl;
-  pl.n_calls = n_calls;
-  pl.n_keys = call_off[n_calls];
-  pl.group_off.push_back(0);
-  pl.call_quad_off.push_back(0);
-  pl.key_idx.reserve(pl.n_keys);
-  size_t maxc = 0;
-  for (size_t c = 0; c < n_calls; ++c) maxc = std::max<size_t>(maxc, call_off[c + 1] - call_off[c]);
-  size_t cap = 16;
-  while (cap < 2 * maxc) cap <<= 1;
-  std::vector<uint32_t> slot(cap), stamp(cap, 0), gid(maxc), first, cnt, pos, flat(maxc);
-  std::vector<int32_t> pairs;
-  auto same = [&](uint32_t a, uint32_t b) { return mlen == 0 || std::memcmp(msgs + mlen * a, msgs + mlen * b, mlen) == 0; };
-  for (size_t c = 0; c < n_calls; ++c) {
-    const uint32_t b0 = call_off[c], e0 = call_off[c + 1], gen = (uint32_t)c + 1;
-    first.clear();
-    cnt.clear();
-    for (uint32_t i = b0; i < e0; ++i) {
-      size_t h = mlen ? (size_t)msg_hash(msgs + mlen * (size_t)i, mlen) & (cap - 1) : 0;
-      while (true) {
-        if (stamp[h] != gen) {
-          stamp[h] = gen;
-          slot[h] = (uint32_t)first.size();
-          first.push_back(i);
-          cnt.push_back(0);
-          break;
-        }
-        if (same(first[slot[h]], i)) break;
-        h = (h + 1) & (cap - 1);
-      }
-      gid[i - b0] = slot[h];
-      ++cnt[slot[h]];
-    }
-    const size_t ng = first.size();
-    pos.assign(ng + 1, 0);
-    for (size_t g = 0; g < ng; ++g) pos[g + 1] = pos[g] + cnt[g];
-    for (uint32_t i = b0; i < e0; ++i) flat[pos[gid[i - b0]]++] = i;   // pos[g] ends at group g's end
-    pairs.clear();
-    for (size_t g = 0; g < ng; ++g) {
-      const uint32_t* m = flat.data() + pos[g] - cnt[g];
-      if (h_pks) {
-        bool all_inf = true;
-        for (uint32_t k = 0; k < cnt[g] && all_inf; ++k) all_inf = is_inf_encoding(h_pks + 48 * (size_t)m[k], 48);
-        if (all_inf) continue;
-      }
-      pl.key_idx.insert(pl.key_idx.end(), m, m + cnt[g]);
-      pl.group_off.push_back((uint32_t)pl.key_idx.size());
-      pl.group_msg.insert(pl.group_msg.end(), msgs + mlen * first[g], msgs + mlen * (first[g] + 1));
-      pl.group_call.push_back((uint32_t)c);
-      pairs.push_back((int32_t)pl.G);
-      ++pl.G;
-    }
-    if (with_sig[c] && !(h_sigs && is_inf_encoding(h_sigs + 96 * c, 96))) pairs.push_back(-(int32_t)c - 1);
-    if (pairs.empty()) pairs.push_back(PAIR_NONE);   // the empty product: one idle quad, f = 1
-    for (size_t k = 0; k < pairs.size(); k += 2) {
-      pl.quad_pair.push_back(pairs[k]);
-      pl.quad_pair.push_back(k + 1 < pairs.size() ? pairs[k + 1] : PAIR_NONE);
-    }
-    pl.call_quad_off.push_back((uint32_t)(pl.quad_pair.size() / 2));
-  }
-  finish_plan(pl);
-  if (pl.G) pl.agg = plan_agg(pl.G, pl.group_off.data());
-  return pl;
-}
-
-// Host plan from caller-given groups (bls381_verify_multiple_grouped_device): the same
-// VmPlan as plan_vm, with key_idx the caller's key order; groups of one call with equal
-// messages are merged (first-occurrence order), empty groups dropped.
-VmPlan plan_vm_grouped(size_t n_calls, const uint32_t* call_group_off, const uint32_t* group_key_off,
-                       const uint8_t* msgs, size_t mlen) {
-  VmPlan pl;
-  pl.n_calls = n_calls;
-  const size_t ng_all = call_group_off[n_calls];
-  pl.n_keys = group_key_off[ng_all];
-  pl.group_off.push_back(0);
-  pl.call_quad_off.push_back(0);
-  pl.key_idx.reserve(pl.n_keys);
-  size_t maxc = 0;
-  for (size_t c = 0; c < n_calls; ++c) maxc = std::max<size_t>(maxc, call_group_off[c + 1] - call_group_off[c]);
-  size_t cap = 16;
-  while (cap < 2 * maxc) cap <<= 1;
-  std::vector<uint32_t> slot(cap), stamp(cap, 0), first, merged;
-  std::vector<std::vector<uint32_t>> extra;   // later groups merged into a distinct message (rare)
-  std::vector<int32_t> pairs;
-  auto same = [&](uint32_t a, uint32_t b) { return mlen == 0 || std::memcmp(msgs + mlen * a, msgs + mlen * b, mlen) == 0; };
-  for (size_t c = 0; c < n_calls; ++c) {
-    const uint32_t gen = (uint32_t)c + 1;
-    first.clear();
-    extra.clear();
-    for (uint32_t g = call_group_off[c]; g < call_group_off[c + 1]; ++g) {
-      if (group_key_off[g + 1] == group_key_off[g]) continue;   // the empty aggregate: pairing 1
-      size_t h = mlen ? (size_t)msg_hash(msgs + mlen * (size_t)g, mlen) & (cap - 1) : 0;
-      while (true) {
-        if (stamp[h] != gen) {
-          stamp[h] = gen;
-          slot[h] = (uint32_t)first.size();
-          first.push_back(g);
-          extra.emplace_back();
-          break;
-        }
-        if (same(first[slot[h]], g)) { extra[slot[h]].push_back(g); break; }
-        h = (h + 1) & (cap - 1);
-      }
-    }
-    pairs.clear();
-    for (size_t d = 0; d < first.size(); ++d) {
-      for (uint32_t k = group_key_off[first[d]]; k < group_key_off[first[d] + 1]; ++k) pl.key_idx.push_back(k);
-      for (uint32_t g : extra[d])
-        for (uint32_t k = group_key_off[g]; k < group_key_off[g + 1]; ++k) pl.key_idx.push_back(k);
-      pl.group_off.push_back((uint32_t)pl.key_idx.size());
-      pl.group_msg.insert(pl.group_msg.end(), msgs + mlen * first[d], msgs + mlen * (first[d] + 1));
-      pl.group_call.push_back((uint32_t)c);
-      pairs.push_back((int32_t)pl.G);
-      ++pl.G;
-    }
-    pairs.push_back(-(int32_t)c - 1);   // the signature pair (an infinite signature is idle on the device)
-    for (size_t k = 0; k < pairs.size(); k += 2) {
-      pl.quad_pair.push_back(pairs[k]);
-      pl.quad_pair.push_back(k + 1 < pairs.size() ? pairs[k + 1] : PAIR_NONE);
-    }
-    pl.call_quad_off.push_back((uint32_t)(pl.quad_pair.size() / 2));
-  }
-  finish_plan(pl);
-  if (pl.G) pl.agg = plan_agg(pl.G, pl.group_off.data());
-  return pl;
-}
+// (the host plan of a batch, VmPlan / plan_vm / plan_vm_grouped, and the segmented product
+// passes, plan_products: bls381_plan.hpp)
 
 // Each lane quad runs (up to) two pairs of one call, one per half (bls381_quad.hpp).
 // A half's pair is idle for PAIR_NONE or an infinite operand (py_ecc: pairing 1);
@@ -1072,6 +686,24 @@ __global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_fp12_chunk_product
   if (!pr_odd()) out_st[c] = st;
 }
 
+// Queues the segmented product passes over the n_in values f / st; f and st become the last
+// pass's outputs (one value per segment).  The chunk lists are async-copy sources: the caller
+// keeps `passes` alive until the stream has passed them.
+int run_product_passes(Bump& b, hipStream_t s, const ProductPasses& passes, uint32_t*& f, uint8_t*& st, size_t n_in) {
+  for (const auto& chunks : passes) {
+    agg_chunk* d_ch = b.take<agg_chunk>(chunks.size());
+    uint32_t* nf = b.take<uint32_t>(12 * FP_LIMBS * chunks.size());
+    uint8_t* nst = b.take<uint8_t>(chunks.size());
+    HIPC(hipMemcpyAsync(d_ch, chunks.data(), chunks.size() * sizeof(agg_chunk), hipMemcpyHostToDevice, s));
+    LAUNCH("fp12_product", s, dim3(grid_for(2 * chunks.size())), dim3(KBLOCK), k_fp12_chunk_product, chunks.size(),
+           (const agg_chunk*)d_ch, (const uint32_t*)f, n_in, (const uint8_t*)st, nf, nst);
+    f = nf;
+    st = nst;
+    n_in = chunks.size();
+  }
+  return 0;
+}
+
 // rows idx[k] of `src` (row_bytes each) -> dst row k
 __global__ void __launch_bounds__(KBLOCK) k_gather_rows(size_t n, const uint32_t* __restrict__ idx,
                                                         const uint8_t* __restrict__ src, uint32_t row_bytes,
@@ -1202,7 +834,7 @@ int run_vm_batch(Ctx* c, const VmPlan& pl, size_t mlen, const uint8_t* d_pks, co
         LAUNCH("hash_search", s, dim3(grid_for(16 * G)), dim3(KBLOCK), k_hash_search<16>, G, (const uint8_t*)d_gmsg,
                (uint32_t)mlen, (const uint8_t*)d_gdom, 8, d_koff);
       if (!wide && !pl.tasks)
-        LAUNCH_HASH(s, G, (const uint8_t*)d_gmsg, (uint32_t)mlen, (const uint8_t*)d_gdom, 8, h_aff, h_st);
+        TRY(launch_hash_g2(s, G, (const uint8_t*)d_gmsg, (uint32_t)mlen, (const uint8_t*)d_gdom, 8, h_aff, h_st));
       else if (int rc_h = launch_hash_koff(s, G, (const uint8_t*)d_gmsg, (uint32_t)mlen, (const uint8_t*)d_gdom, 8,
                                            h_aff, h_st, (const uint32_t*)(wide ? d_koff : nullptr), pl.tasks ? 1 : 0))
         return rc_h;
@@ -1211,74 +843,22 @@ int run_vm_batch(Ctx* c, const VmPlan& pl, size_t mlen, const uint8_t* d_pks, co
     HIPC(hipStreamWaitEvent(s, c->ev_join2, 0));
   }
   if (pl.tasks) {
-    // BLS381_ML_OCTET: one octet per pair task while the tasks fit one wave per SIMD
-    static const int ml_octet = env_knob("BLS381_ML_OCTET", 1);
-    if (ml_octet && nf <= 8192)
-      LAUNCH("miller_tasks_o1", s, dim3(grid_for(8 * nf)), dim3(KBLOCK), k_miller_tasks<8>, nf, (const int32_t*)d_qp,
-             G, (const uint32_t*)h_aff, (const uint8_t*)h_st, (const uint32_t*)agg_aff, (const uint8_t*)agg_st, ncalls,
-             (const uint32_t*)sig_aff, (const uint8_t*)sig_st, (const uint32_t*)nullptr, nf, f, st);
-    else
-      LAUNCH("miller_tasks_q1", s, dim3(grid_for(4 * nf)), dim3(KBLOCK), k_miller_tasks<4>, nf, (const int32_t*)d_qp,
-             G, (const uint32_t*)h_aff, (const uint8_t*)h_st, (const uint32_t*)agg_aff, (const uint8_t*)agg_st, ncalls,
-             (const uint32_t*)sig_aff, (const uint8_t*)sig_st, (const uint32_t*)nullptr, nf, f, st);
+    // one octet per pair task while the tasks fit one wave per SIMD, else (or BLS381_ML_OCTET=0) one quad
+    const bool oct = ml_octet() && nf <= 8192;
+    LAUNCH(oct ? "miller_tasks_o1" : "miller_tasks_q1", s, dim3(grid_for((oct ? 8 : 4) * nf)), dim3(KBLOCK),
+           (oct ? k_miller_tasks<8> : k_miller_tasks<4>), nf, (const int32_t*)d_qp, G, (const uint32_t*)h_aff,
+           (const uint8_t*)h_st, (const uint32_t*)agg_aff, (const uint8_t*)agg_st, ncalls, (const uint32_t*)sig_aff,
+           (const uint8_t*)sig_st, (const uint32_t*)nullptr, nf, f, st);
   } else {
     LAUNCH("miller_quads", s, dim3(grid_for(4 * nq)), dim3(KBLOCK), k_miller_quads, nq, (const int32_t*)d_qp, G,
            (const uint32_t*)h_aff, (const uint8_t*)h_st, (const uint32_t*)agg_aff, (const uint8_t*)agg_st, ncalls,
            (const uint32_t*)sig_aff, (const uint8_t*)sig_st, (const uint32_t*)d_qslot, nf, f, st);
   }
   // segmented products (chunk lists live in the plan, which outlives the stream work)
-  size_t n_in = nf;
-  for (const auto& chunks : pl.tasks ? pl.task_passes : pl.passes) {
-    agg_chunk* d_ch = b.take<agg_chunk>(chunks.size());
-    uint32_t* nf = b.take<uint32_t>(12 * FP_LIMBS * chunks.size());
-    uint8_t* nst = b.take<uint8_t>(chunks.size());
-    HIPC(hipMemcpyAsync(d_ch, chunks.data(), chunks.size() * sizeof(agg_chunk), hipMemcpyHostToDevice, s));
-    LAUNCH("fp12_product", s, dim3(grid_for(2 * chunks.size())), dim3(KBLOCK), k_fp12_chunk_product, chunks.size(),
-           (const agg_chunk*)d_ch, (const uint32_t*)f, n_in, (const uint8_t*)st, nf, nst);
-    f = nf;
-    st = nst;
-    n_in = chunks.size();
-  }
+  TRY(run_product_passes(b, s, pl.product_passes(), f, st, nf));
   *out_f = f;
   *out_st = st;
   return 0;
-}
-
-// workspace bound of run_vm_batch for a plan (plus the final verdict bytes)
-size_t vm_ws_bound(const VmPlan& pl, size_t mlen) {
-  const size_t G = pl.G + 1, nq = pl.nquads + 1, nc = pl.n_calls + 1, nk = pl.key_idx.size() + 1;
-  size_t s = 1 << 16;
-  s += align256(4 * nk) + align256(G * mlen + 1) + align256(4 * G) + align256(8 * G + 1) + align256(48 * nk) +
-       align256(8 * nq);
-  s += align256(2 * FPW * G) + align256(G) + align256(4 * FPW * G) + align256(G) + align256(4 * G);
-  s += agg_ws_size(pl.agg, 3) + 256;
-  s += align256(4 * FPW * nc) + align256(nc);
-  s += align256(12 * FPW * (2 * nq + nc)) + align256(2 * nq + nc) + align256(4 * nq) + 2 * align256(4 * nc);
-  for (const auto& ch : pl.tasks ? pl.task_passes : pl.passes)
-    s += align256(ch.size() * sizeof(agg_chunk)) + align256(12 * FPW * ch.size()) + align256(ch.size());
-  s += align256(nc);
-  return s;
-}
-
-// the same bound from sizes alone (device entry point: the caller sizes the workspace before the plan exists)
-size_t vm_ws_bound_sizes(size_t n_calls, size_t n_keys, size_t mlen) {
-  const size_t G = n_keys + 1, nq = n_keys / 2 + n_calls + 1, nc = n_calls + 1, nk = n_keys + 1;
-  size_t s = 1 << 16;
-  s += align256(4 * nk) + align256(G * mlen + 1) + align256(4 * G) + align256(8 * G + 1) + align256(48 * nk) +
-       align256(8 * nq);
-  s += align256(2 * FPW * G) + align256(G) + align256(4 * FPW * G) + align256(G) + align256(4 * G);
-  // group-sum levels: chunks <= groups + keys / CHUNK per level, three levels at most below 2^27 keys
-  const size_t chunks = G + n_keys / CHUNK_MIN + 1;
-  s += 3 * (align256(chunks * sizeof(agg_chunk)) + align256(chunks * 3 * FPW) + align256(chunks)) + 256;
-  s += align256(4 * FPW * nc) + align256(nc);
-  // Miller values: quads, or two pair tasks per quad on the latency path
-  s += align256(12 * FPW * (2 * nq + nc)) + align256(2 * nq + nc) + align256(4 * nq) + 2 * align256(4 * nc);
-  // product passes: <= nt / 8 + n_calls chunks per pass over nt <= 2 nq values, and the
-  // sizes shrink 8x per pass
-  const size_t pc = nq / 2 + 2 * nc;
-  s += 8 * (align256(pc * sizeof(agg_chunk)) + align256(12 * FPW * pc) + align256(pc));
-  s += align256(nc);
-  return s;
 }
 
 }  // namespace
@@ -1408,34 +988,21 @@ int bls381_verify_batch_device(size_t n, const uint8_t* d_pks, const uint8_t* d_
 }
 
 int bls381_verify_batch(size_t n, const uint8_t* pks, const uint8_t* msgs32, const uint8_t* sigs,
-                        const uint8_t* dom8s, uint8_t* verdicts_out) try {
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  if (n == 0) return 0;
-  if (!pks || !msgs32 || !sigs || !dom8s || !verdicts_out) return BLS381_EARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t in_bytes = align256(48 * n) + align256(32 * n) + align256(96 * n) + align256(8 * n) + align256(n);
-  if ((rc = ensure_ws(c, in_bytes + verify_ws_size(n) + 1024))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_pks = b.take<uint8_t>(48 * n);
-  uint8_t* d_msgs = b.take<uint8_t>(32 * n);
-  uint8_t* d_sigs = b.take<uint8_t>(96 * n);
-  uint8_t* d_doms = b.take<uint8_t>(8 * n);
-  uint8_t* d_v = b.take<uint8_t>(n);
-  void* ws = b.take<uint8_t>(verify_ws_size(n));
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_pks, pks, 48 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_msgs, msgs32, 32 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_sigs, sigs, 96 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_doms, dom8s, 8 * n, hipMemcpyHostToDevice, s));
-  if ((rc = run_verify_batch(c, n, d_pks, d_msgs, d_sigs, d_doms, d_v, ws, s))) return rc;
-  HIPC(hipMemcpyAsync(verdicts_out, d_v, n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                        const uint8_t* dom8s, uint8_t* verdicts_out) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    if (n == 0) return 0;
+    if (!pks || !msgs32 || !sigs || !dom8s || !verdicts_out) return BLS381_EARG;
+    HostCall hc(c);
+    VerifyIn d;
+    TRY(hc.carve([&](Bump& b) { d.carve(b, n, verify_ws_size(n)); }));
+    TRY(d.upload(hc, n, pks, msgs32, sigs, dom8s));
+    TRY(run_verify_batch(c, n, d.pks, d.msgs, d.sigs, d.doms, d.v, d.ws, hc.s));
+    TRY(hc.download(verdicts_out, d.v, n));
+    return hc.finish();
+  });
 }
 
 // BLS381_LAT_PAD = k > 1 (measurement knob, default 1 = off): a single call runs as a batch of k
@@ -1475,51 +1042,50 @@ int bls381_verify(const uint8_t pk[48], const uint8_t* msg, size_t msg_len, cons
   return bls381_verify_multiple(1, pk, msg, msg_len, sig, dom8);
 }
 
-// host buffers -> device copies -> the planned pipeline (keys dropped from the plan when all-infinite)
-static int vm_host(Ctx* c, size_t n_calls, const uint32_t* call_off, const uint8_t* pks, const uint8_t* msgs,
+// host buffers -> device copies -> the planned pipeline (keys dropped from the plan when all-infinite);
+// `b` becomes the pipeline's workspace (vm_ws_bound bytes), from which the caller takes its outputs
+static int vm_host(HostCall& hc, size_t n_calls, const uint32_t* call_off, const uint8_t* pks, const uint8_t* msgs,
                    size_t msg_len, const uint8_t* sigs, const uint8_t* dom8s, const int* with_sig, Bump& b,
                    uint32_t** f, uint8_t** st) {
   const size_t nk = call_off[n_calls];
   auto pl = std::make_shared<VmPlan>(plan_vm(n_calls, call_off, msgs, msg_len, pks, sigs, with_sig));
-  int rc;
-  if ((rc = ensure_ws(c, vm_ws_bound(*pl, msg_len) + align256(48 * nk + 1) + align256(96 * n_calls) +
-                             align256(8 * n_calls) + 4096)))
-    return rc;
-  b = Bump(c->ws, c->ws_cap);
-  uint8_t* d_pks = b.take<uint8_t>(48 * nk + 1);
-  uint8_t* d_sigs = b.take<uint8_t>(96 * n_calls);
-  uint8_t* d_doms = b.take<uint8_t>(8 * n_calls);
-  hipStream_t s = c->stream;
-  if (nk) HIPC(hipMemcpyAsync(d_pks, pks, 48 * nk, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_sigs, sigs, 96 * n_calls, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_doms, dom8s, 8 * n_calls, hipMemcpyHostToDevice, s));
-  if ((rc = run_vm_batch(c, *pl, msg_len, d_pks, d_sigs, d_doms, b, s, f, st))) return rc;
-  return keep_until_done(c, s, pl);   // the plan's arrays are async copy sources
+  const size_t ws_bytes = vm_ws_bound(*pl, msg_len);
+  uint8_t *d_pks, *d_sigs, *d_doms, *ws;
+  TRY(hc.carve([&](Bump& in) {
+    d_pks = in.take<uint8_t>(48 * nk + 1);
+    d_sigs = in.take<uint8_t>(96 * n_calls);
+    d_doms = in.take<uint8_t>(8 * n_calls);
+    ws = in.take<uint8_t>(ws_bytes);
+  }));
+  b = Bump(ws, ws_bytes);
+  TRY(hc.upload(d_pks, pks, 48 * nk));
+  TRY(hc.upload(d_sigs, sigs, 96 * n_calls));
+  TRY(hc.upload(d_doms, dom8s, 8 * n_calls));
+  TRY(run_vm_batch(hc.c, *pl, msg_len, d_pks, d_sigs, d_doms, b, hc.s, f, st));
+  return keep_until_done(hc.c, hc.s, pl);   // the plan's arrays are async copy sources
 }
 
 int bls381_verify_multiple_batch(size_t n_calls, const uint32_t* call_off, const uint8_t* pks,
                                  const uint8_t* msgs, size_t msg_len, const uint8_t* sigs, const uint8_t* dom8s,
-                                 uint8_t* verdicts) try {
-  if (n_calls == 0) return 0;
-  if (!call_off || !sigs || !dom8s || !verdicts || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
-  if (call_off[n_calls] && (!pks || (!msgs && msg_len))) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::vector<int> with_sig(n_calls, 1);
-  Bump b(nullptr, 0);
-  uint32_t* f;
-  uint8_t* st;
-  if ((rc = vm_host(c, n_calls, call_off, pks, msgs, msg_len, sigs, dom8s, with_sig.data(), b, &f, &st))) return rc;
-  uint8_t* d_v = b.take<uint8_t>(n_calls);
-  LAUNCH_FE(c->stream, n_calls, f, st, d_v);
-  HIPC(hipMemcpyAsync(verdicts, d_v, n_calls, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                 uint8_t* verdicts) {
+  return guarded([&]() -> int {
+    if (n_calls == 0) return 0;
+    if (!call_off || !sigs || !dom8s || !verdicts || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
+    if (call_off[n_calls] && (!pks || (!msgs && msg_len))) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    std::vector<int> with_sig(n_calls, 1);
+    Bump b;
+    uint32_t* f;
+    uint8_t* st;
+    TRY(vm_host(hc, n_calls, call_off, pks, msgs, msg_len, sigs, dom8s, with_sig.data(), b, &f, &st));
+    uint8_t* d_v = b.take<uint8_t>(n_calls);
+    LAUNCH_FE(hc.s, n_calls, f, st, d_v);
+    TRY(hc.download(verdicts, d_v, n_calls));
+    return hc.finish();
+  });
 }
 
 size_t bls381_verify_multiple_batch_workspace_size(size_t n_calls, size_t n_pks, size_t msg_len) {
@@ -1529,64 +1095,81 @@ size_t bls381_verify_multiple_batch_workspace_size(size_t n_calls, size_t n_pks,
 int bls381_verify_multiple_batch_device(size_t n_calls, const uint32_t* h_call_off, const uint8_t* h_msgs,
                                         size_t msg_len, const uint8_t* d_pks, const uint8_t* d_sigs,
                                         const uint8_t* d_dom8s, uint8_t* d_verdicts, void* d_workspace,
-                                        void* stream) try {
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  if (n_calls == 0) return 0;
-  if (!h_call_off || !d_sigs || !d_dom8s || !d_verdicts || !d_workspace || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
-  const size_t nk = h_call_off[n_calls];
-  if (h_call_off[0] != 0 || (nk && (!d_pks || (!h_msgs && msg_len)))) return BLS381_EARG;
-  for (size_t k = 0; k < n_calls; ++k)
-    if (h_call_off[k + 1] < h_call_off[k]) return BLS381_EARG;
-  std::vector<int> with_sig(n_calls, 1);
-  auto pl = std::make_shared<VmPlan>(plan_vm(n_calls, h_call_off, h_msgs, msg_len, nullptr, nullptr, with_sig.data()));
-  hipStream_t s = (hipStream_t)stream;
-  Bump b(d_workspace, bls381_verify_multiple_batch_workspace_size(n_calls, nk, msg_len));
-  uint32_t* f;
-  uint8_t* st;
-  if ((rc = run_vm_batch(c, *pl, msg_len, d_pks, d_sigs, d_dom8s, b, s, &f, &st))) return rc;
-  LAUNCH_FE(s, n_calls, f, st, d_verdicts);
-  return keep_until_done(c, s, pl);   // the plan's arrays are async copy sources
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                        void* stream) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    if (n_calls == 0) return 0;
+    if (!h_call_off || !d_sigs || !d_dom8s || !d_verdicts || !d_workspace || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
+    const size_t nk = h_call_off[n_calls];
+    if (h_call_off[0] != 0 || (nk && (!d_pks || (!h_msgs && msg_len)))) return BLS381_EARG;
+    for (size_t k = 0; k < n_calls; ++k)
+      if (h_call_off[k + 1] < h_call_off[k]) return BLS381_EARG;
+    std::vector<int> with_sig(n_calls, 1);
+    auto pl = std::make_shared<VmPlan>(plan_vm(n_calls, h_call_off, h_msgs, msg_len, nullptr, nullptr, with_sig.data()));
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_verify_multiple_batch_workspace_size(n_calls, nk, msg_len));
+    uint32_t* f;
+    uint8_t* st;
+    if ((rc = run_vm_batch(c, *pl, msg_len, d_pks, d_sigs, d_dom8s, b, s, &f, &st))) return rc;
+    LAUNCH_FE(s, n_calls, f, st, d_verdicts);
+    return keep_until_done(c, s, pl);   // the plan's arrays are async copy sources
+  });
 }
 
 size_t bls381_verify_multiple_grouped_workspace_size(size_t n_calls, size_t n_groups, size_t n_pks, size_t msg_len) {
   return vm_ws_bound_sizes(n_calls, std::max(n_pks, n_groups), msg_len) + align256(n_calls) + 4096;
 }
 
+// argument check shared by the grouped device entries (d_keys: compressed keys or registry entries)
+static bool grouped_args_ok(size_t n_calls, const uint32_t* h_call_group_off, size_t n_groups,
+                            const uint32_t* h_group_key_off, const uint8_t* h_group_msgs, size_t msg_len,
+                            const void* d_keys, const uint8_t* d_sigs, const uint8_t* d_dom8s,
+                            const uint8_t* d_verdicts, const void* d_workspace) {
+  if (!h_call_group_off || !h_group_key_off || !d_sigs || !d_dom8s || !d_verdicts || !d_workspace ||
+      msg_len > BLS381_MSG_MAX)
+    return false;
+  if (h_call_group_off[0] != 0 || h_call_group_off[n_calls] != n_groups || h_group_key_off[0] != 0) return false;
+  for (size_t k = 0; k < n_calls; ++k)
+    if (h_call_group_off[k + 1] < h_call_group_off[k]) return false;
+  for (size_t g = 0; g < n_groups; ++g)
+    if (h_group_key_off[g + 1] < h_group_key_off[g]) return false;
+  const size_t nk = h_group_key_off[n_groups];
+  return !((nk && !d_keys) || (n_groups && msg_len && !h_group_msgs));
+}
+
+// plan and queue a grouped batch on `stream`; reg: the keys are registry entries
+static int vm_grouped_device(Ctx* c, size_t n_calls, const uint32_t* h_call_group_off, size_t n_groups,
+                             const uint32_t* h_group_key_off, const uint8_t* h_group_msgs, size_t msg_len,
+                             const uint8_t* d_keys, const uint8_t* d_sigs, const uint8_t* d_dom8s, uint8_t* d_verdicts,
+                             void* d_workspace, void* stream, const agg_reg_src* reg) {
+  auto pl = std::make_shared<VmPlan>(plan_vm_grouped(n_calls, h_call_group_off, h_group_key_off, h_group_msgs, msg_len));
+  hipStream_t s = (hipStream_t)stream;
+  Bump b(d_workspace, bls381_verify_multiple_grouped_workspace_size(n_calls, n_groups, h_group_key_off[n_groups], msg_len));
+  uint32_t* f;
+  uint8_t* st;
+  TRY(run_vm_batch(c, *pl, msg_len, d_keys, d_sigs, d_dom8s, b, s, &f, &st, reg));
+  LAUNCH_FE(s, n_calls, f, st, d_verdicts);
+  return keep_until_done(c, s, pl);   // the plan's arrays are async copy sources
+}
+
 int bls381_verify_multiple_grouped_device(size_t n_calls, const uint32_t* h_call_group_off, size_t n_groups,
                                           const uint32_t* h_group_key_off, const uint8_t* h_group_msgs,
                                           size_t msg_len, const uint8_t* d_pks, const uint8_t* d_sigs,
                                           const uint8_t* d_dom8s, uint8_t* d_verdicts, void* d_workspace,
-                                          void* stream) try {
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  if (n_calls == 0) return 0;
-  if (!h_call_group_off || !h_group_key_off || !d_sigs || !d_dom8s || !d_verdicts || !d_workspace ||
-      msg_len > BLS381_MSG_MAX)
-    return BLS381_EARG;
-  if (h_call_group_off[0] != 0 || h_call_group_off[n_calls] != n_groups || h_group_key_off[0] != 0) return BLS381_EARG;
-  for (size_t k = 0; k < n_calls; ++k)
-    if (h_call_group_off[k + 1] < h_call_group_off[k]) return BLS381_EARG;
-  for (size_t g = 0; g < n_groups; ++g)
-    if (h_group_key_off[g + 1] < h_group_key_off[g]) return BLS381_EARG;
-  const size_t nk = h_group_key_off[n_groups];
-  if ((nk && !d_pks) || (n_groups && msg_len && !h_group_msgs)) return BLS381_EARG;
-  auto pl = std::make_shared<VmPlan>(plan_vm_grouped(n_calls, h_call_group_off, h_group_key_off, h_group_msgs, msg_len));
-  hipStream_t s = (hipStream_t)stream;
-  Bump b(d_workspace, bls381_verify_multiple_grouped_workspace_size(n_calls, n_groups, nk, msg_len));
-  uint32_t* f;
-  uint8_t* st;
-  if ((rc = run_vm_batch(c, *pl, msg_len, d_pks, d_sigs, d_dom8s, b, s, &f, &st))) return rc;
-  LAUNCH_FE(s, n_calls, f, st, d_verdicts);
-  return keep_until_done(c, s, pl);
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                          void* stream) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    if (n_calls == 0) return 0;
+    if (!grouped_args_ok(n_calls, h_call_group_off, n_groups, h_group_key_off, h_group_msgs, msg_len, d_pks, d_sigs,
+                         d_dom8s, d_verdicts, d_workspace))
+      return BLS381_EARG;
+    return vm_grouped_device(c, n_calls, h_call_group_off, n_groups, h_group_key_off, h_group_msgs, msg_len, d_pks,
+                             d_sigs, d_dom8s, d_verdicts, d_workspace, stream, nullptr);
+  });
 }
 
 int bls381_verify_multiple(size_t n, const uint8_t* pks, const uint8_t* msgs, size_t msg_len, const uint8_t sig[96],
@@ -1616,67 +1199,60 @@ int bls381_verify_multiple(size_t n, const uint8_t* pks, const uint8_t* msgs, si
 }
 
 int bls381_miller_partial(size_t n, const uint8_t* pks, const uint8_t* msgs, size_t msg_len, const uint8_t sig[96],
-                          int include_sig, const uint8_t dom8[8], uint8_t out576[576]) try {
-  if ((n && (!pks || (!msgs && msg_len))) || !sig || !dom8 || !out576 || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const uint32_t off[2] = {0, (uint32_t)n};
-  const int with_sig = include_sig ? 1 : 0;
-  Bump b(nullptr, 0);
-  uint32_t* f;
-  uint8_t* st;
-  if ((rc = vm_host(c, 1, off, pks, msgs, msg_len, sig, dom8, &with_sig, b, &f, &st))) return rc;
-  uint8_t* d_out = b.take<uint8_t>(576);
-  LAUNCH("fp12_to_bytes", c->stream, dim3(1), dim3(KBLOCK), k_fp12_to_bytes, (size_t)1, (const uint32_t*)f, d_out);
-  uint8_t h_st = 0;
-  HIPC(hipMemcpyAsync(out576, d_out, 576, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipMemcpyAsync(&h_st, st, 1, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return h_st == ST_OK ? 0 : 1;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                          int include_sig, const uint8_t dom8[8], uint8_t out576[576]) {
+  return guarded([&]() -> int {
+    if ((n && (!pks || (!msgs && msg_len))) || !sig || !dom8 || !out576 || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const uint32_t off[2] = {0, (uint32_t)n};
+    const int with_sig = include_sig ? 1 : 0;
+    Bump b;
+    uint32_t* f;
+    uint8_t* st;
+    TRY(vm_host(hc, 1, off, pks, msgs, msg_len, sig, dom8, &with_sig, b, &f, &st));
+    uint8_t* d_out = b.take<uint8_t>(576);
+    LAUNCH("fp12_to_bytes", hc.s, dim3(1), dim3(KBLOCK), k_fp12_to_bytes, (size_t)1, (const uint32_t*)f, d_out);
+    uint8_t h_st = 0;
+    TRY(hc.download(out576, d_out, 576));
+    TRY(hc.download(&h_st, st, 1));
+    TRY(hc.finish());
+    return h_st == ST_OK ? 0 : 1;
+  });
 }
 
-int bls381_final_verify(size_t k, const uint8_t* parts576) try {
-  if (k == 0 || !parts576) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, 4 * (align256(576 * k) + align256(12 * FPW * k) + align256(k) + 1024) + 8192))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  hipStream_t s = c->stream;
-  uint8_t* d_in = b.take<uint8_t>(576 * k);
-  uint32_t* f = b.take<uint32_t>(12 * FP_LIMBS * k);
-  uint8_t* st = b.take<uint8_t>(k);
-  HIPC(hipMemcpyAsync(d_in, parts576, 576 * k, hipMemcpyHostToDevice, s));
-  HIPC(hipMemsetAsync(st, 0, k, s));
-  LAUNCH("fp12_from_bytes", s, dim3(grid_for(2 * k)), dim3(KBLOCK), k_fp12_from_bytes, k, (const uint8_t*)d_in, f);
-  const auto passes = plan_products({0u, (uint32_t)k});
-  size_t n_in = k;
-  for (const auto& chunks : passes) {
-    agg_chunk* d_ch = b.take<agg_chunk>(chunks.size());
-    uint32_t* nf = b.take<uint32_t>(12 * FP_LIMBS * chunks.size());
-    uint8_t* nst = b.take<uint8_t>(chunks.size());
-    HIPC(hipMemcpyAsync(d_ch, chunks.data(), chunks.size() * sizeof(agg_chunk), hipMemcpyHostToDevice, s));
-    LAUNCH("fp12_product", s, dim3(grid_for(2 * chunks.size())), dim3(KBLOCK), k_fp12_chunk_product, chunks.size(),
-           (const agg_chunk*)d_ch, (const uint32_t*)f, n_in, (const uint8_t*)st, nf, nst);
-    f = nf;
-    st = nst;
-    n_in = chunks.size();
-  }
-  uint8_t* d_v = b.take<uint8_t>(1);
-  LAUNCH_FE(s, (size_t)1, f, st, d_v);
-  uint8_t v = 0;
-  HIPC(hipMemcpyAsync(&v, d_v, 1, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return v;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+int bls381_final_verify(size_t k, const uint8_t* parts576) {
+  return guarded([&]() -> int {
+    if (k == 0 || !parts576) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const auto passes = plan_products({0u, (uint32_t)k});   // alive until finish()
+    uint8_t *d_in, *st, *d_v;
+    uint32_t* f;
+    Bump pb;   // the product passes' slices
+    TRY(hc.carve([&](Bump& b) {
+      d_in = b.take<uint8_t>(576 * k);
+      f = b.take<uint32_t>(12 * FP_LIMBS * k);
+      st = b.take<uint8_t>(k);
+      d_v = b.take<uint8_t>(1);
+      size_t pass_bytes = 0;
+      for (const auto& ch : passes) pass_bytes += chunk_level_bytes(ch.size(), 12);
+      pb = Bump(b.take<uint8_t>(pass_bytes), pass_bytes);
+    }));
+    hipStream_t s = hc.s;
+    TRY(hc.upload(d_in, parts576, 576 * k));
+    HIPC(hipMemsetAsync(st, 0, k, s));
+    LAUNCH("fp12_from_bytes", s, dim3(grid_for(2 * k)), dim3(KBLOCK), k_fp12_from_bytes, k, (const uint8_t*)d_in, f);
+    TRY(run_product_passes(pb, s, passes, f, st, k));
+    LAUNCH_FE(s, (size_t)1, f, st, d_v);
+    uint8_t v = 0;
+    TRY(hc.download(&v, d_v, 1));
+    TRY(hc.finish());
+    return v;
+  });
 }
 
 // ---- aggregation
@@ -1711,53 +1287,58 @@ static size_t agg_ws_bytes(int is_g2, size_t ng, const uint32_t* offsets) {
 }
 
 size_t bls381_aggregate_pubkeys_batch_workspace_size(size_t n_groups, size_t n_pks) {
-  // worst case chunking: every group splits into ceil(size/CHUNK) chunks, plus levels
-  const size_t chunks = n_groups + n_pks / CHUNK_MIN + 1;
-  return 8192 + 3 * (align256(chunks * sizeof(agg_chunk)) + align256(chunks * 3 * FPW) + align256(chunks));
+  return agg_ws_bound_sizes(n_groups, n_pks);
 }
 
 int bls381_aggregate_pubkeys_batch_device(size_t n_groups, const uint32_t* h_offsets, size_t n_pks,
                                           const uint8_t* d_pks, uint8_t* d_out48, int32_t* d_status,
-                                          void* d_workspace, void* stream) try {
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  if (n_groups == 0) return 0;
-  if (!h_offsets || !d_out48 || !d_status || !d_workspace || (n_pks && !d_pks)) return BLS381_EARG;
-  hipStream_t s = (hipStream_t)stream;   // NULL = the HIP null stream (torch's default stream)
-  return agg_batch_impl(c, 0, n_groups, h_offsets, n_pks, d_pks, d_out48, d_status, d_workspace,
-                        bls381_aggregate_pubkeys_batch_workspace_size(n_groups, n_pks), s, policy_flags(0));
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                          void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    if (n_groups == 0) return 0;
+    if (!h_offsets || !d_out48 || !d_status || !d_workspace || (n_pks && !d_pks)) return BLS381_EARG;
+    hipStream_t s = (hipStream_t)stream;   // NULL = the HIP null stream (torch's default stream)
+    return agg_batch_impl(c, 0, n_groups, h_offsets, n_pks, d_pks, d_out48, d_status, d_workspace,
+                          bls381_aggregate_pubkeys_batch_workspace_size(n_groups, n_pks), s, policy_flags(0));
+  });
 }
 
-static int agg_host(int is_g2, size_t ng, const uint32_t* offsets, const uint8_t* pts, uint8_t* out,
-                    int32_t* status) try {
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t bytes = is_g2 ? 96 : 48;
-  const size_t npts = offsets[ng];
-  const size_t need = align256(npts * bytes + 1) + align256(ng * bytes) + align256(ng * 4) + agg_ws_bytes(is_g2, ng, offsets) + 4096;
-  if ((rc = ensure_ws(c, need))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_pts = b.take<uint8_t>(npts * bytes + 1);
-  uint8_t* d_out = b.take<uint8_t>(ng * bytes);
-  int32_t* d_st = b.take<int32_t>(ng);
-  hipStream_t s = c->stream;
-  if (npts) HIPC(hipMemcpyAsync(d_pts, pts, npts * bytes, hipMemcpyHostToDevice, s));
-  if ((rc = agg_batch_impl(c, is_g2, ng, offsets, npts, d_pts, d_out, d_st, b.base + align256(b.off),
-                           b.left() > 256 ? b.left() - 256 : 0, s, policy_flags(0))))
-    return rc;
-  HIPC(hipMemcpyAsync(out, d_out, ng * bytes, hipMemcpyDeviceToHost, s));
-  HIPC(hipMemcpyAsync(status, d_st, ng * 4, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+// The host form of a grouped aggregation (plain or registry): in_bytes of input copied in, `run(d_in,
+// d_out, d_status, ws)` queued on the context stream with a workspace of ws_bytes, then ng results of
+// out_bytes each and ng statuses copied back.
+extern "C++" template <class Run>
+int agg_host_call(HostCall& hc, size_t ng, const void* in, size_t in_bytes, size_t out_bytes, size_t ws_bytes,
+                         uint8_t* out, int32_t* status, Run&& run) {
+  uint8_t *d_in, *d_out, *d_ws;
+  int32_t* d_st;
+  TRY(hc.carve([&](Bump& b) {
+    d_in = b.take<uint8_t>(in_bytes + 1);
+    d_out = b.take<uint8_t>(ng * out_bytes);
+    d_st = b.take<int32_t>(ng);
+    d_ws = b.take<uint8_t>(ws_bytes);
+  }));
+  TRY(hc.upload(d_in, in, in_bytes));
+  TRY(run(d_in, d_out, d_st, d_ws));
+  TRY(hc.download(out, d_out, ng * out_bytes));
+  TRY(hc.download(status, d_st, ng * 4));
+  return hc.finish();
+}
+
+static int agg_host(int is_g2, size_t ng, const uint32_t* offsets, const uint8_t* pts, uint8_t* out, int32_t* status) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t bytes = is_g2 ? 96 : 48, npts = offsets[ng], wsb = agg_ws_bytes(is_g2, ng, offsets);
+    return agg_host_call(hc, ng, pts, npts * bytes, bytes, wsb, out, status,
+                         [&](uint8_t* d_pts, uint8_t* d_out, int32_t* d_st, uint8_t* d_ws) {
+                           return agg_batch_impl(c, is_g2, ng, offsets, npts, d_pts, d_out, d_st, d_ws, wsb, hc.s,
+                                                 policy_flags(0));
+                         });
+  });
 }
 
 int bls381_aggregate_pubkeys_batch(size_t n_groups, const uint32_t* offsets, const uint8_t* pks, uint8_t* out48,
@@ -1788,155 +1369,114 @@ int bls381_aggregate_g2(size_t n, const uint8_t* sigs, uint8_t out[96]) {
   return bls381_aggregate_signatures(n, sigs, out);
 }
 
-// ---- single-item helpers (fixtures / reference API)
-int bls381_sign(const uint8_t* msg, size_t msg_len, const uint8_t sk[32], const uint8_t dom8[8], uint8_t out[96]) try {
-  if ((!msg && msg_len) || !sk || !dom8 || !out || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
+// ---- signing / key / hash helpers (fixtures / reference API); the single-item forms are one-item batches
+static int sign_impl(size_t n, const uint8_t* msgs, size_t msg_len, const uint8_t* sks, const uint8_t* dom8s,
+                     uint8_t* out96) {
   int rc = 0;
   Ctx* c = get_ctx(&rc);
   if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, 4096))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_msg = b.take<uint8_t>(msg_len + 1);
-  uint8_t* d_sk = b.take<uint8_t>(32);
-  uint8_t* d_dom = b.take<uint8_t>(8);
-  uint8_t* d_out = b.take<uint8_t>(96);
-  hipStream_t s = c->stream;
-  if (msg_len) HIPC(hipMemcpyAsync(d_msg, msg, msg_len, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_sk, sk, 32, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_dom, dom8, 8, hipMemcpyHostToDevice, s));
-  LAUNCH("sign", s, dim3(1), dim3(KBLOCK), k_sign, (size_t)1, (const uint8_t*)d_msg, (uint32_t)msg_len,
+  HostCall hc(c);
+  uint8_t *d_msg, *d_sk, *d_dom, *d_out;
+  TRY(hc.carve([&](Bump& b) {
+    d_msg = b.take<uint8_t>(msg_len * n + 1);
+    d_sk = b.take<uint8_t>(32 * n);
+    d_dom = b.take<uint8_t>(8 * n);
+    d_out = b.take<uint8_t>(96 * n);
+  }));
+  TRY(hc.upload(d_msg, msgs, msg_len * n));
+  TRY(hc.upload(d_sk, sks, 32 * n));
+  TRY(hc.upload(d_dom, dom8s, 8 * n));
+  LAUNCH("sign", hc.s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_sign, n, (const uint8_t*)d_msg, (uint32_t)msg_len,
          (const uint8_t*)d_sk, (const uint8_t*)d_dom, d_out);
-  HIPC(hipMemcpyAsync(out, d_out, 96, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+  TRY(hc.download(out96, d_out, 96 * n));
+  return hc.finish();
 }
 
-int bls381_sign_batch(size_t n, const uint8_t* msgs32, const uint8_t* sks, const uint8_t* dom8s, uint8_t* out96) try {
+int bls381_sign(const uint8_t* msg, size_t msg_len, const uint8_t sk[32], const uint8_t dom8[8], uint8_t out[96]) {
+  if ((!msg && msg_len) || !sk || !dom8 || !out || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
+  return guarded([&] { return sign_impl(1, msg, msg_len, sk, dom8, out); });
+}
+
+int bls381_sign_batch(size_t n, const uint8_t* msgs32, const uint8_t* sks, const uint8_t* dom8s, uint8_t* out96) {
   if (n == 0) return 0;
   if (!msgs32 || !sks || !dom8s || !out96) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, align256(32 * n) * 2 + align256(8 * n) + align256(96 * n) + 4096))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_msg = b.take<uint8_t>(32 * n);
-  uint8_t* d_sk = b.take<uint8_t>(32 * n);
-  uint8_t* d_dom = b.take<uint8_t>(8 * n);
-  uint8_t* d_out = b.take<uint8_t>(96 * n);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_msg, msgs32, 32 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_sk, sks, 32 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_dom, dom8s, 8 * n, hipMemcpyHostToDevice, s));
-  LAUNCH("sign", s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_sign, n, (const uint8_t*)d_msg, (uint32_t)32,
-         (const uint8_t*)d_sk, (const uint8_t*)d_dom, d_out);
-  HIPC(hipMemcpyAsync(out96, d_out, 96 * n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+  return guarded([&] { return sign_impl(n, msgs32, 32, sks, dom8s, out96); });
 }
 
-int bls381_privtopub_batch(size_t n, const uint8_t* sks, uint8_t* out48) try {
+int bls381_privtopub_batch(size_t n, const uint8_t* sks, uint8_t* out48) {
   if (n == 0) return 0;
   if (!sks || !out48) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, align256(32 * n) + align256(48 * n) + 4096))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_sk = b.take<uint8_t>(32 * n);
-  uint8_t* d_out = b.take<uint8_t>(48 * n);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_sk, sks, 32 * n, hipMemcpyHostToDevice, s));
-  LAUNCH("privtopub", s, dim3(grid_for(n)), dim3(KBLOCK), k_privtopub, n, (const uint8_t*)d_sk, d_out);
-  HIPC(hipMemcpyAsync(out48, d_out, 48 * n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t *d_sk, *d_out;
+    TRY(hc.carve([&](Bump& b) {
+      d_sk = b.take<uint8_t>(32 * n);
+      d_out = b.take<uint8_t>(48 * n);
+    }));
+    TRY(hc.upload(d_sk, sks, 32 * n));
+    LAUNCH("privtopub", hc.s, dim3(grid_for(n)), dim3(KBLOCK), k_privtopub, n, (const uint8_t*)d_sk, d_out);
+    TRY(hc.download(out48, d_out, 48 * n));
+    return hc.finish();
+  });
 }
 
-int bls381_privtopub(const uint8_t sk[32], uint8_t out[48]) try {
+int bls381_privtopub(const uint8_t sk[32], uint8_t out[48]) {
   if (!sk || !out) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, 4096))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_sk = b.take<uint8_t>(32);
-  uint8_t* d_out = b.take<uint8_t>(48);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_sk, sk, 32, hipMemcpyHostToDevice, s));
-  LAUNCH("privtopub", s, dim3(1), dim3(KBLOCK), k_privtopub, (size_t)1, (const uint8_t*)d_sk, d_out);
-  HIPC(hipMemcpyAsync(out, d_out, 48, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+  return bls381_privtopub_batch(1, sk, out);
 }
 
 int bls381_hash_to_g2(const uint8_t* msg, size_t msg_len, const uint8_t dom8[8], uint8_t out_compressed[96],
-                      uint8_t out_affine[192]) try {
+                      uint8_t out_affine[192]) {
   if ((!msg && msg_len) || !dom8 || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, 4096))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_msg = b.take<uint8_t>(msg_len + 1);
-  uint8_t* d_dom = b.take<uint8_t>(8);
-  uint8_t* d_comp = b.take<uint8_t>(96);
-  uint8_t* d_aff = b.take<uint8_t>(192);
-  hipStream_t s = c->stream;
-  if (msg_len) HIPC(hipMemcpyAsync(d_msg, msg, msg_len, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_dom, dom8, 8, hipMemcpyHostToDevice, s));
-  LAUNCH("hash_to_g2", s, dim3(1), dim3(KBLOCK), k_hash_g2_out, (size_t)1, (const uint8_t*)d_msg, (uint32_t)msg_len,
-         (const uint8_t*)d_dom, d_comp, d_aff);
-  if (out_compressed) HIPC(hipMemcpyAsync(out_compressed, d_comp, 96, hipMemcpyDeviceToHost, s));
-  if (out_affine) HIPC(hipMemcpyAsync(out_affine, d_aff, 192, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t *d_msg, *d_dom, *d_comp, *d_aff;
+    TRY(hc.carve([&](Bump& b) {
+      d_msg = b.take<uint8_t>(msg_len + 1);
+      d_dom = b.take<uint8_t>(8);
+      d_comp = b.take<uint8_t>(96);
+      d_aff = b.take<uint8_t>(192);
+    }));
+    TRY(hc.upload(d_msg, msg, msg_len));
+    TRY(hc.upload(d_dom, dom8, 8));
+    LAUNCH("hash_to_g2", hc.s, dim3(1), dim3(KBLOCK), k_hash_g2_out, (size_t)1, (const uint8_t*)d_msg,
+           (uint32_t)msg_len, (const uint8_t*)d_dom, d_comp, d_aff);
+    if (out_compressed) TRY(hc.download(out_compressed, d_comp, 96));
+    if (out_affine) TRY(hc.download(out_affine, d_aff, 192));
+    return hc.finish();
+  });
 }
 
-int bls381_hash_to_g2_pyecc_projective(size_t n, const uint8_t* msgs32, const uint8_t* dom8s, uint8_t* out288) try {
+int bls381_hash_to_g2_pyecc_projective(size_t n, const uint8_t* msgs32, const uint8_t* dom8s, uint8_t* out288) {
   if (n == 0) return 0;
   if (!msgs32 || !dom8s || !out288) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t scratch = (size_t)n * H2_BITS * 6 * FPW;
-  if ((rc = ensure_ws(c, align256(32 * n) + align256(8 * n) + align256(288 * n) + align256(scratch) + 4096))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_msgs = b.take<uint8_t>(32 * n);
-  uint8_t* d_doms = b.take<uint8_t>(8 * n);
-  uint8_t* d_out = b.take<uint8_t>(288 * n);
-  uint32_t* d_scr = b.take<uint32_t>(scratch / 4);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_msgs, msgs32, 32 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_doms, dom8s, 8 * n, hipMemcpyHostToDevice, s));
-  LAUNCH("hash_to_g2_pyecc", s, dim3(grid_for(2 * n, 64)), dim3(64), k_hash_g2_pyecc, n, (const uint8_t*)d_msgs,
-         (const uint8_t*)d_doms, d_scr, d_out);
-  HIPC(hipMemcpyAsync(out288, d_out, 288 * n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t scratch = (size_t)n * H2_BITS * 6 * FPW;
+    uint8_t *d_msgs, *d_doms, *d_out;
+    uint32_t* d_scr;
+    TRY(hc.carve([&](Bump& b) {
+      d_msgs = b.take<uint8_t>(32 * n);
+      d_doms = b.take<uint8_t>(8 * n);
+      d_out = b.take<uint8_t>(288 * n);
+      d_scr = b.take<uint32_t>(scratch / 4);
+    }));
+    TRY(hc.upload(d_msgs, msgs32, 32 * n));
+    TRY(hc.upload(d_doms, dom8s, 8 * n));
+    LAUNCH("hash_to_g2_pyecc", hc.s, dim3(grid_for(2 * n, 64)), dim3(64), k_hash_g2_pyecc, n, (const uint8_t*)d_msgs,
+           (const uint8_t*)d_doms, d_scr, d_out);
+    TRY(hc.download(out288, d_out, 288 * n));
+    return hc.finish();
+  });
 }
 
 // ---- pubkey registry
@@ -2031,30 +1571,30 @@ int bls381_registry_add(bls381_registry* reg, size_t n, const uint8_t* pks48, in
   return nbad;
 }
 
-int bls381_registry_lookup(bls381_registry* reg, size_t n, const uint8_t* pks48, int32_t* entry_out) try {
-  if (!reg || (n && (!pks48 || !entry_out))) return BLS381_EARG;
-  if (n == 0) return 0;
-  int rc = 0;
-  Ctx* c = registry_ctx(reg, &rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lr(reg->mu);
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, align256(48 * n) + align256(4 * n) + 1024))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_q = b.take<uint8_t>(48 * n);
-  int32_t* d_e = b.take<int32_t>(n);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_q, pks48, 48 * n, hipMemcpyHostToDevice, s));
-  LAUNCH("registry_lookup", s, dim3(grid_for(n)), dim3(KBLOCK), k_reg_lookup, n, (const uint8_t*)d_q,
-         (const uint8_t*)reg->keys, (const uint32_t*)reg->table, reg->tmask, d_e);
-  HIPC(hipMemcpyAsync(entry_out, d_e, 4 * n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  int hits = 0;
-  for (size_t i = 0; i < n; ++i) hits += entry_out[i] >= 0;
-  return hits;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+int bls381_registry_lookup(bls381_registry* reg, size_t n, const uint8_t* pks48, int32_t* entry_out) {
+  return guarded([&]() -> int {
+    if (!reg || (n && (!pks48 || !entry_out))) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = registry_ctx(reg, &rc);
+    if (!c) return rc;
+    std::lock_guard<std::mutex> lr(reg->mu);
+    HostCall hc(c);
+    uint8_t* d_q;
+    int32_t* d_e;
+    TRY(hc.carve([&](Bump& b) {
+      d_q = b.take<uint8_t>(48 * n);
+      d_e = b.take<int32_t>(n);
+    }));
+    TRY(hc.upload(d_q, pks48, 48 * n));
+    LAUNCH("registry_lookup", hc.s, dim3(grid_for(n)), dim3(KBLOCK), k_reg_lookup, n, (const uint8_t*)d_q,
+           (const uint8_t*)reg->keys, (const uint32_t*)reg->table, reg->tmask, d_e);
+    TRY(hc.download(entry_out, d_e, 4 * n));
+    TRY(hc.finish());
+    int hits = 0;
+    for (size_t i = 0; i < n; ++i) hits += entry_out[i] >= 0;
+    return hits;
+  });
 }
 
 // groups of registry entries (d_entry, device) or of compressed keys looked up first (d_pks); one pass of the
@@ -2087,19 +1627,18 @@ size_t bls381_registry_aggregate_workspace_size(size_t n_groups, size_t n_in) {
 
 int bls381_registry_aggregate_indices_device(bls381_registry* reg, size_t n_groups, const uint32_t* h_offsets,
                                              size_t n_idx, const uint32_t* d_indices, uint8_t* d_out48,
-                                             int32_t* d_status, void* d_workspace, void* stream) try {
-  if (!reg || !h_offsets || !d_out48 || !d_status || !d_workspace || (n_idx && !d_indices)) return BLS381_EARG;
-  if (n_groups == 0) return 0;
-  if (h_offsets[n_groups] != n_idx) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = registry_ctx(reg, &rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lr(reg->mu);
-  return registry_agg_impl(c, reg, n_groups, h_offsets, n_idx, (const int32_t*)d_indices, nullptr, d_out48, d_status,
-                           d_workspace, bls381_registry_aggregate_workspace_size(n_groups, n_idx), (hipStream_t)stream);
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                             int32_t* d_status, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!reg || !h_offsets || !d_out48 || !d_status || !d_workspace || (n_idx && !d_indices)) return BLS381_EARG;
+    if (n_groups == 0) return 0;
+    if (h_offsets[n_groups] != n_idx) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = registry_ctx(reg, &rc);
+    if (!c) return rc;
+    std::lock_guard<std::mutex> lr(reg->mu);
+    return registry_agg_impl(c, reg, n_groups, h_offsets, n_idx, (const int32_t*)d_indices, nullptr, d_out48, d_status,
+                             d_workspace, bls381_registry_aggregate_workspace_size(n_groups, n_idx), (hipStream_t)stream);
+  });
 }
 
 int bls381_registry_verify_multiple_grouped_device(bls381_registry* reg, size_t n_calls,
@@ -2107,66 +1646,38 @@ int bls381_registry_verify_multiple_grouped_device(bls381_registry* reg, size_t 
                                                    const uint32_t* h_group_key_off, const uint8_t* h_group_msgs,
                                                    size_t msg_len, const uint32_t* d_entries, const uint8_t* d_sigs,
                                                    const uint8_t* d_dom8s, uint8_t* d_verdicts, void* d_workspace,
-                                                   void* stream) try {
-  if (!reg) return BLS381_EARG;
-  if (n_calls == 0) return 0;
-  if (!h_call_group_off || !h_group_key_off || !d_sigs || !d_dom8s || !d_verdicts || !d_workspace ||
-      msg_len > BLS381_MSG_MAX)
-    return BLS381_EARG;
-  if (h_call_group_off[0] != 0 || h_call_group_off[n_calls] != n_groups || h_group_key_off[0] != 0) return BLS381_EARG;
-  for (size_t k = 0; k < n_calls; ++k)
-    if (h_call_group_off[k + 1] < h_call_group_off[k]) return BLS381_EARG;
-  for (size_t g = 0; g < n_groups; ++g)
-    if (h_group_key_off[g + 1] < h_group_key_off[g]) return BLS381_EARG;
-  const size_t nk = h_group_key_off[n_groups];
-  if ((nk && !d_entries) || (n_groups && msg_len && !h_group_msgs)) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = registry_ctx(reg, &rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lr(reg->mu);
-  auto pl = std::make_shared<VmPlan>(plan_vm_grouped(n_calls, h_call_group_off, h_group_key_off, h_group_msgs, msg_len));
-  hipStream_t s = (hipStream_t)stream;
-  Bump b(d_workspace, bls381_verify_multiple_grouped_workspace_size(n_calls, n_groups, nk, msg_len));
-  const agg_reg_src src{nullptr, reg->aff, reg->st, reg->cap, reg->size};
-  uint32_t* f;
-  uint8_t* st;
-  if ((rc = run_vm_batch(c, *pl, msg_len, (const uint8_t*)d_entries, d_sigs, d_dom8s, b, s, &f, &st, &src))) return rc;
-  LAUNCH_FE(s, n_calls, f, st, d_verdicts);
-  return keep_until_done(c, s, pl);
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                                   void* stream) {
+  return guarded([&]() -> int {
+    if (!reg) return BLS381_EARG;
+    if (n_calls == 0) return 0;
+    if (!grouped_args_ok(n_calls, h_call_group_off, n_groups, h_group_key_off, h_group_msgs, msg_len, d_entries, d_sigs,
+                         d_dom8s, d_verdicts, d_workspace))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = registry_ctx(reg, &rc);
+    if (!c) return rc;
+    std::lock_guard<std::mutex> lr(reg->mu);
+    const agg_reg_src src{nullptr, reg->aff, reg->st, reg->cap, reg->size};
+    return vm_grouped_device(c, n_calls, h_call_group_off, n_groups, h_group_key_off, h_group_msgs, msg_len,
+                             (const uint8_t*)d_entries, d_sigs, d_dom8s, d_verdicts, d_workspace, stream, &src);
+  });
 }
 
 static int registry_agg_host(bls381_registry* reg, size_t ng, const uint32_t* offsets, const uint32_t* indices,
-                             const uint8_t* pks, uint8_t* out48, int32_t* status) try {
-  int rc = 0;
-  Ctx* c = registry_ctx(reg, &rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lr(reg->mu);
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t n_in = offsets[ng];
-  const size_t wsb = bls381_registry_aggregate_workspace_size(ng, n_in);
-  const size_t need = align256(n_in * (indices ? 4 : 48) + 1) + align256(48 * ng) + align256(4 * ng) + wsb + 1024;
-  if ((rc = ensure_ws(c, need))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_in = b.take<uint8_t>(n_in * (indices ? 4 : 48) + 1);
-  uint8_t* d_out = b.take<uint8_t>(48 * ng);
-  int32_t* d_st = b.take<int32_t>(ng);
-  uint8_t* d_ws = b.take<uint8_t>(wsb);
-  hipStream_t s = c->stream;
-  if (n_in) HIPC(hipMemcpyAsync(d_in, indices ? (const void*)indices : (const void*)pks, n_in * (indices ? 4 : 48),
-                                hipMemcpyHostToDevice, s));
-  if ((rc = registry_agg_impl(c, reg, ng, offsets, n_in, indices ? (const int32_t*)d_in : nullptr,
-                              indices ? nullptr : d_in, d_out, d_st, d_ws, wsb, s)))
-    return rc;
-  HIPC(hipMemcpyAsync(out48, d_out, 48 * ng, hipMemcpyDeviceToHost, s));
-  HIPC(hipMemcpyAsync(status, d_st, 4 * ng, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                             const uint8_t* pks, uint8_t* out48, int32_t* status) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = registry_ctx(reg, &rc);
+    if (!c) return rc;
+    std::lock_guard<std::mutex> lr(reg->mu);
+    HostCall hc(c);
+    const size_t n_in = offsets[ng], wsb = bls381_registry_aggregate_workspace_size(ng, n_in);
+    return agg_host_call(hc, ng, indices ? (const void*)indices : (const void*)pks, n_in * (indices ? 4 : 48), 48, wsb,
+                         out48, status, [&](uint8_t* d_in, uint8_t* d_out, int32_t* d_st, uint8_t* d_ws) {
+                           return registry_agg_impl(c, reg, ng, offsets, n_in, indices ? (const int32_t*)d_in : nullptr,
+                                                    indices ? nullptr : d_in, d_out, d_st, d_ws, wsb, hc.s);
+                         });
+  });
 }
 
 int bls381_registry_aggregate_indices(bls381_registry* reg, size_t n_groups, const uint32_t* offsets,
@@ -2184,145 +1695,132 @@ int bls381_registry_aggregate_pubkeys_batch(bls381_registry* reg, size_t n_group
 }
 
 // ---- SSZ roots and the deposit pipeline
-size_t bls381_ssz_root_workspace_size(void) { return align256(4 * SSZ_PROG_MAX) + 256; }
-
-static int ssz_root_impl(size_t n, const uint8_t* d_items, size_t stride, const uint32_t* h_prog, uint32_t plen,
-                         uint8_t* d_roots, Bump& b, hipStream_t s, Ctx* c) {
-  uint32_t* d_prog = b.take<uint32_t>(SSZ_PROG_MAX);
-  int32_t* d_err = b.take<int32_t>(1);
-  auto prog = std::make_shared<std::vector<uint32_t>>(h_prog, h_prog + plen);
-  HIPC(hipMemcpyAsync(d_prog, prog->data(), 4 * plen, hipMemcpyHostToDevice, s));
-  HIPC(hipMemsetAsync(d_err, 0, 4, s));
-  LAUNCH("ssz_root", s, dim3(grid_for(n)), dim3(KBLOCK), k_ssz_root, n, d_items, stride, (const uint32_t*)d_prog,
-         plen, d_roots, d_err);
-  return keep_until_done(c, s, prog);
+// (ssz_prog_ok and the deposit signing program: bls381_plan.hpp)
+struct SszWs {
+  uint32_t* prog;
+  int32_t* err;
+};
+static SszWs carve_ssz(Bump& b) {
+  SszWs w;
+  w.prog = b.take<uint32_t>(SSZ_PROG_MAX);
+  w.err = b.take<int32_t>(1);
+  return w;
+}
+size_t bls381_ssz_root_workspace_size(void) {
+  return carved_bytes([](Bump& b) { carve_ssz(b); });
 }
 
-// host check of a program: balanced stack, chunk reads inside the item, sizes in bounds (the kernel
-// re-checks the stack; reads past the item are what this rules out)
-static bool ssz_prog_ok(const uint32_t* prog, uint32_t plen, size_t item_size) {
-  if (!prog || plen == 0 || plen > SSZ_PROG_MAX) return false;
-  int sp = 0, peak = 0;
-  for (uint32_t pc = 0; pc < plen;) {
-    if (prog[pc] == SSZ_CHUNK && pc + 2 < plen) {
-      if (prog[pc + 2] > 32 || (size_t)prog[pc + 1] + prog[pc + 2] > item_size) return false;
-      ++sp; pc += 3;
-    } else if (prog[pc] == SSZ_MERKLE && pc + 1 < plen) {
-      const uint32_t k = prog[pc + 1];
-      if (k == 0 || (int)k > sp) return false;
-      uint32_t p = 1;
-      while (p < k) p <<= 1;
-      if (sp - (int)k + (int)p > peak) peak = sp - (int)k + (int)p;
-      sp = sp - (int)k + 1; pc += 2;
-    } else {
-      return false;
-    }
-    if (sp > peak) peak = sp;
-  }
-  return sp == 1 && peak <= SSZ_STACK;
+static int ssz_root_impl(size_t n, const uint8_t* d_items, size_t stride, const uint32_t* h_prog, uint32_t plen,
+                         uint8_t* d_roots, const SszWs& w, hipStream_t s, Ctx* c) {
+  auto prog = std::make_shared<std::vector<uint32_t>>(h_prog, h_prog + plen);
+  HIPC(hipMemcpyAsync(w.prog, prog->data(), 4 * plen, hipMemcpyHostToDevice, s));
+  HIPC(hipMemsetAsync(w.err, 0, 4, s));
+  LAUNCH("ssz_root", s, dim3(grid_for(n)), dim3(KBLOCK), k_ssz_root, n, d_items, stride, (const uint32_t*)w.prog,
+         plen, d_roots, w.err);
+  return keep_until_done(c, s, prog);
 }
 
 int bls381_ssz_root_batch_device(size_t n, const uint8_t* d_items, size_t stride, size_t item_size,
                                  const uint32_t* h_prog, uint32_t prog_len, uint8_t* d_roots32, void* d_workspace,
-                                 void* stream) try {
-  if (n == 0) return 0;
-  if (!d_items || !d_roots32 || !d_workspace || stride < item_size || !ssz_prog_ok(h_prog, prog_len, item_size))
-    return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  Bump b(d_workspace, bls381_ssz_root_workspace_size());
-  return ssz_root_impl(n, d_items, stride, h_prog, prog_len, d_roots32, b, (hipStream_t)stream, c);
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                 void* stream) {
+  return guarded([&]() -> int {
+    if (n == 0) return 0;
+    if (!d_items || !d_roots32 || !d_workspace || stride < item_size || !ssz_prog_ok(h_prog, prog_len, item_size))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    Bump b(d_workspace, bls381_ssz_root_workspace_size());
+    return ssz_root_impl(n, d_items, stride, h_prog, prog_len, d_roots32, carve_ssz(b), (hipStream_t)stream, c);
+  });
 }
 
 int bls381_ssz_root_batch(size_t n, const uint8_t* items, size_t item_size, const uint32_t* prog, uint32_t prog_len,
-                          uint8_t* roots32) try {
-  if (n == 0) return 0;
-  if (!items || !roots32 || item_size == 0 || !ssz_prog_ok(prog, prog_len, item_size)) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = ensure_ws(c, align256(n * item_size) + align256(32 * n) + bls381_ssz_root_workspace_size() + 1024)))
-    return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_items = b.take<uint8_t>(n * item_size);
-  uint8_t* d_roots = b.take<uint8_t>(32 * n);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_items, items, n * item_size, hipMemcpyHostToDevice, s));
-  if ((rc = ssz_root_impl(n, d_items, item_size, prog, prog_len, d_roots, b, s, c))) return rc;
-  HIPC(hipMemcpyAsync(roots32, d_roots, 32 * n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                          uint8_t* roots32) {
+  return guarded([&]() -> int {
+    if (n == 0) return 0;
+    if (!items || !roots32 || item_size == 0 || !ssz_prog_ok(prog, prog_len, item_size)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t *d_items, *d_roots;
+    SszWs w;
+    TRY(hc.carve([&](Bump& b) {
+      d_items = b.take<uint8_t>(n * item_size);
+      d_roots = b.take<uint8_t>(32 * n);
+      w = carve_ssz(b);
+    }));
+    TRY(hc.upload(d_items, items, n * item_size));
+    TRY(ssz_root_impl(n, d_items, item_size, prog, prog_len, d_roots, w, hc.s, c));
+    TRY(hc.download(roots32, d_roots, 32 * n));
+    return hc.finish();
+  });
 }
 
-// signing_root(DepositData) (0_beacon-chain.md:394-403; ssz_impl.py:158-163): pubkey Bytes48 (2 chunks),
-// withdrawal_credentials Bytes32, amount uint64; the signature field is left out
-static const uint32_t DEPOSIT_SIGNING_PROG[] = {SSZ_CHUNK, 0, 32, SSZ_CHUNK, 32, 16, SSZ_MERKLE, 2,
-                                                SSZ_CHUNK, 48, 32, SSZ_CHUNK, 80, 8, SSZ_MERKLE, 3};
-constexpr size_t DEPOSIT_DATA_BYTES = 48 + 32 + 8 + 96;
-
+// the deposit pipeline's workspace: the gathered keys and signatures, the signing roots, the root
+// program's and the verify batch's own
+struct DepositWs {
+  uint8_t *pks, *sigs, *roots;
+  SszWs ssz;
+  void* verify;
+};
+static DepositWs carve_deposits(Bump& b, size_t n) {
+  DepositWs w;
+  w.pks = b.take<uint8_t>(48 * n);
+  w.sigs = b.take<uint8_t>(96 * n);
+  w.roots = b.take<uint8_t>(32 * n);
+  w.ssz = carve_ssz(b);
+  w.verify = b.take<uint8_t>(verify_ws_size(n));
+  return w;
+}
 size_t bls381_verify_deposits_workspace_size(size_t n) {
-  return align256(48 * n) + align256(96 * n) + align256(32 * n) + bls381_ssz_root_workspace_size() +
-         verify_ws_size(n) + 2048;
+  return carved_bytes([&](Bump& b) { carve_deposits(b, n); });
 }
 
 int bls381_verify_deposits_device(size_t n, const uint8_t* d_deposit_data, const uint8_t* d_dom8s,
-                                  uint8_t* d_verdicts, void* d_workspace, void* stream) try {
-  if (n == 0) return 0;
-  if (!d_deposit_data || !d_dom8s || !d_verdicts || !d_workspace) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Bump b(d_workspace, bls381_verify_deposits_workspace_size(n));
-  uint8_t* pks = b.take<uint8_t>(48 * n);
-  uint8_t* sigs = b.take<uint8_t>(96 * n);
-  uint8_t* roots = b.take<uint8_t>(32 * n);
-  LAUNCH("gather_pubkeys", s, dim3(grid_for(48 * n)), dim3(KBLOCK), k_gather_field, n, d_deposit_data,
-         DEPOSIT_DATA_BYTES, 0u, 48u, pks);
-  LAUNCH("gather_signatures", s, dim3(grid_for(96 * n)), dim3(KBLOCK), k_gather_field, n, d_deposit_data,
-         DEPOSIT_DATA_BYTES, 88u, 96u, sigs);
-  if ((rc = ssz_root_impl(n, d_deposit_data, DEPOSIT_DATA_BYTES, DEPOSIT_SIGNING_PROG,
-                          (uint32_t)(sizeof(DEPOSIT_SIGNING_PROG) / 4), roots, b, s, c)))
-    return rc;
-  void* vws = b.take<uint8_t>(verify_ws_size(n));
-  return run_verify_batch(c, n, pks, roots, sigs, d_dom8s, d_verdicts, vws, s);
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                  uint8_t* d_verdicts, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (n == 0) return 0;
+    if (!d_deposit_data || !d_dom8s || !d_verdicts || !d_workspace) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_verify_deposits_workspace_size(n));
+    const DepositWs w = carve_deposits(b, n);
+    LAUNCH("gather_pubkeys", s, dim3(grid_for(48 * n)), dim3(KBLOCK), k_gather_field, n, d_deposit_data,
+           DEPOSIT_DATA_BYTES, 0u, 48u, w.pks);
+    LAUNCH("gather_signatures", s, dim3(grid_for(96 * n)), dim3(KBLOCK), k_gather_field, n, d_deposit_data,
+           DEPOSIT_DATA_BYTES, 88u, 96u, w.sigs);
+    TRY(ssz_root_impl(n, d_deposit_data, DEPOSIT_DATA_BYTES, DEPOSIT_SIGNING_PROG, DEPOSIT_SIGNING_PROG_LEN, w.roots,
+                      w.ssz, s, c));
+    return run_verify_batch(c, n, w.pks, w.roots, w.sigs, d_dom8s, d_verdicts, w.verify, s);
+  });
 }
 
-int bls381_verify_deposits(size_t n, const uint8_t* deposit_data, const uint8_t* dom8s, uint8_t* verdicts) try {
-  if (n == 0) return 0;
-  if (!deposit_data || !dom8s || !verdicts) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t wsb = bls381_verify_deposits_workspace_size(n);
-  if ((rc = ensure_ws(c, align256(DEPOSIT_DATA_BYTES * n) + align256(8 * n) + align256(n) + wsb + 1024))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_dd = b.take<uint8_t>(DEPOSIT_DATA_BYTES * n);
-  uint8_t* d_dom = b.take<uint8_t>(8 * n);
-  uint8_t* d_ver = b.take<uint8_t>(n);
-  uint8_t* d_ws = b.take<uint8_t>(wsb);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_dd, deposit_data, DEPOSIT_DATA_BYTES * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_dom, dom8s, 8 * n, hipMemcpyHostToDevice, s));
-  if ((rc = bls381_verify_deposits_device(n, d_dd, d_dom, d_ver, d_ws, s))) return rc;
-  HIPC(hipMemcpyAsync(verdicts, d_ver, n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+int bls381_verify_deposits(size_t n, const uint8_t* deposit_data, const uint8_t* dom8s, uint8_t* verdicts) {
+  return guarded([&]() -> int {
+    if (n == 0) return 0;
+    if (!deposit_data || !dom8s || !verdicts) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_verify_deposits_workspace_size(n);
+    uint8_t *d_dd, *d_dom, *d_ver, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_dd = b.take<uint8_t>(DEPOSIT_DATA_BYTES * n);
+      d_dom = b.take<uint8_t>(8 * n);
+      d_ver = b.take<uint8_t>(n);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_dd, deposit_data, DEPOSIT_DATA_BYTES * n));
+    TRY(hc.upload(d_dom, dom8s, 8 * n));
+    TRY(bls381_verify_deposits_device(n, d_dd, d_dom, d_ver, d_ws, hc.s));
+    TRY(hc.download(verdicts, d_ver, n));
+    return hc.finish();
+  });
 }
 
 }  // extern "C"
@@ -2475,16 +1973,6 @@ int first_rank(const Comm* cm) { return cm->virt ? 0 : cm->rank; }
 int last_rank(const Comm* cm) { return cm->virt ? cm->nranks - 1 : cm->rank; }
 bool is_root(const Comm* cm) { return cm->virt || cm->rank == 0; }
 
-// runs a rank's local stage of a collective call; exceptions become error codes
-template <class F>
-int local_stage(F&& f) {
-  try {
-    return f();
-  } catch (const std::exception& e) {
-    t_err = e.what();
-    return BLS381_EARG;
-  }
-}
 }  // namespace
 
 extern "C" {
@@ -2601,7 +2089,7 @@ int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* 
   if (!cm) return rc;
   RcclApi* api = cm->virt ? nullptr : rccl_api();
   if (!cm->virt && !api) return BLS381_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
+  HostCall hc(c);   // holds c->mu for the whole call
   const size_t R = (size_t)cm->nranks;
   hipStream_t s = c->stream;
   uint8_t* d_rows;
@@ -2609,7 +2097,7 @@ int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* 
   if (cm->rows_ev) (void)hipEventSynchronize(cm->rows_ev);   // a device-form call may still use them
   uint8_t* d_v = d_rows + 576 * R + 576;
   // local stage: this rank's row(s); on failure the row is zero (verdict False on rank 0)
-  int local = local_stage([&]() -> int {
+  int local = guarded([&]() -> int {
     // distinct message k (first-appearance order) -> rank k mod nranks: a message's
     // pubkey group never straddles two ranks (bls381_amd/sharding.py partition_messages)
     std::unordered_map<std::string, uint32_t> order;
@@ -2633,7 +2121,7 @@ int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* 
       Bump b(nullptr, 0);
       uint32_t* f;
       uint8_t* st;
-      if ((lrc = vm_host(c, 1, off, my_pks.data(), my_msgs.data(), msg_len, sig, dom8, &with_sig, b, &f, &st)))
+      if ((lrc = vm_host(hc, 1, off, my_pks.data(), my_msgs.data(), msg_len, sig, dom8, &with_sig, b, &f, &st)))
         return lrc;
       // this rank's row (576 B, zero when a member is invalid): in place when virtual
       uint8_t* row = cm->virt ? d_rows + 576 * (size_t)r : d_rows + 576 * R;
@@ -2650,7 +2138,7 @@ int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* 
   }
   if (!cm->virt) NCCLC(api, api->all_gather(d_rows + 576 * R, d_rows, 576, ncclUint8, cm->comm, s));
   if (is_root(cm)) {   // one final exponentiation, on rank 0 (verdict 0 if it cannot run)
-    const int root = local_stage([&]() -> int {
+    const int root = guarded([&]() -> int {
       int lrc;
       HIPC(hipMemsetAsync(d_v, 0, 1, s));
       if ((lrc = ensure_ws(c, 12 * FPW * R * 4 + 4 * R + 65536))) return lrc;
@@ -2659,19 +2147,8 @@ int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* 
       uint8_t* gst = b.take<uint8_t>(R);
       HIPC(hipMemsetAsync(gst, ST_OK, R, s));
       LAUNCH("fp12_from_bytes", s, dim3(grid_for(2 * R)), dim3(KBLOCK), k_fp12_from_bytes, R, (const uint8_t*)d_rows, g);
-      auto passes = std::make_shared<std::vector<std::vector<agg_chunk>>>(plan_products({0u, (uint32_t)R}));
-      size_t n_in = R;
-      for (const auto& chunks : *passes) {
-        agg_chunk* d_ch = b.take<agg_chunk>(chunks.size());
-        uint32_t* nf = b.take<uint32_t>(12 * FP_LIMBS * chunks.size());
-        uint8_t* nst = b.take<uint8_t>(chunks.size());
-        HIPC(hipMemcpyAsync(d_ch, chunks.data(), chunks.size() * sizeof(agg_chunk), hipMemcpyHostToDevice, s));
-        LAUNCH("fp12_product", s, dim3(grid_for(2 * chunks.size())), dim3(KBLOCK), k_fp12_chunk_product,
-               chunks.size(), (const agg_chunk*)d_ch, (const uint32_t*)g, n_in, (const uint8_t*)gst, nf, nst);
-        g = nf;
-        gst = nst;
-        n_in = chunks.size();
-      }
+      auto passes = std::make_shared<ProductPasses>(plan_products({0u, (uint32_t)R}));
+      TRY(run_product_passes(b, s, *passes, g, gst, R));
       LAUNCH_FE(s, (size_t)1, g, gst, d_v);
       return keep_until_done(c, s, passes);
     });
@@ -2778,7 +2255,7 @@ static int agg_sharded_impl(Ctx* c, Comm* cm, RcclApi* api, size_t n_local, cons
     const size_t lo = cm->virt ? rr * base + (rr < extra ? rr : extra) : 0;
     const size_t cnt = cm->virt ? base + (rr < extra ? 1 : 0) : n_local;
     // force_err: the caller could not stage its keys (d_workspace may be null): a flagged row only
-    const int lrc = force_err ? force_err : local_stage([&]() -> int {
+    const int lrc = force_err ? force_err : guarded([&]() -> int {
       const uint32_t off1[2] = {0, (uint32_t)cnt};
       auto hold = std::make_shared<AggPlan>(plan_agg(1, off1, 1));
       const uint32_t* jac;
@@ -2801,7 +2278,7 @@ static int agg_sharded_impl(Ctx* c, Comm* cm, RcclApi* api, size_t n_local, cons
   if (local && cm->virt) return local;
   if (!cm->virt) NCCLC(api, api->all_gather(d_rows + row_b * R, d_rows, row_b, ncclUint8, cm->comm, s));
   if (is_root(cm)) {
-    const int root = local_stage([&]() -> int {
+    const int root = guarded([&]() -> int {
       LAUNCH("agg_sum_rows", s, dim3(1), dim3(64), k_agg_sum_rows, (uint32_t)R, (const uint32_t*)d_rows, d_sum, d_st);
       return 0;
     });
@@ -2858,13 +2335,14 @@ int bls381_aggregate_pubkeys_sharded(size_t n, const uint8_t* pks, uint8_t out[4
   const size_t wsl = bls381_aggregate_pubkeys_sharded_device_workspace_size(cnt);
   // result and status in the rows buffer's unused tail (the protocol uses its head)
   uint8_t* d_res = cm->rows + cm->rows_cap - 64;
-  int local = ensure_ws(c, align256(48 * cnt + 1) + wsl);
+  uint8_t* d_pks = nullptr;
   const uint8_t* d_in = nullptr;
   void* w = nullptr;
-  if (!local) {
-    Bump b(c->ws, c->ws_cap);
-    uint8_t* d_pks = b.take<uint8_t>(48 * cnt + 1);
+  int local = carve_ws(c, [&](Bump& b) {
+    d_pks = b.take<uint8_t>(48 * cnt + 1);
     w = b.take<uint8_t>(wsl);
+  });
+  if (!local) {
     if (cnt && hipMemcpyAsync(d_pks, pks + 48 * lo, 48 * cnt, hipMemcpyHostToDevice, s) != hipSuccess)
       local = fail("hipMemcpyAsync", hipGetLastError());
     d_in = d_pks;
@@ -2903,7 +2381,7 @@ int bls381_verify_multiple_batch_sharded(size_t n_calls, const uint32_t* call_of
     const size_t rr = (size_t)r;
     const size_t lo = rr * base + (rr < extra ? rr : extra), cnt = base + (rr < extra ? 1 : 0);
     if (!cnt) continue;
-    const int lrc = local_stage([&]() -> int {
+    const int lrc = guarded([&]() -> int {
       std::vector<uint32_t> off(cnt + 1);
       for (size_t k = 0; k <= cnt; ++k) off[k] = call_off[lo + k] - call_off[lo];
       const size_t k0 = call_off[lo];
@@ -3088,19 +2566,8 @@ int run_verify_randomized(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* m
   int rc = 0;
   std::vector<uint32_t> seg(nb + 1);
   for (size_t k = 0; k <= nb; ++k) seg[k] = (uint32_t)(k * (hb + 1));
-  auto passes = std::make_shared<std::vector<std::vector<agg_chunk>>>(plan_products(seg));
-  size_t n_in = nslots;
-  for (const auto& chunks : *passes) {
-    agg_chunk* d_ch = b.take<agg_chunk>(chunks.size());
-    uint32_t* nf = b.take<uint32_t>(12 * FP_LIMBS * chunks.size());
-    uint8_t* nst = b.take<uint8_t>(chunks.size());
-    HIPC(hipMemcpyAsync(d_ch, chunks.data(), chunks.size() * sizeof(agg_chunk), hipMemcpyHostToDevice, s));
-    LAUNCH("fp12_product", s, dim3(grid_for(2 * chunks.size())), blk, k_fp12_chunk_product, chunks.size(),
-           (const agg_chunk*)d_ch, (const uint32_t*)f, n_in, (const uint8_t*)fst, nf, nst);
-    f = nf;
-    fst = nst;
-    n_in = chunks.size();
-  }
+  const ProductPasses passes = plan_products(seg);   // alive until the synchronise below
+  TRY(run_product_passes(b, s, passes, f, fst, nslots));
   uint8_t* bv = b.take<uint8_t>(nb);
   LAUNCH_FE(s, nb, f, fst, bv);
   std::vector<uint8_t> h_bv(nb), h_cls(n);
@@ -3157,54 +2624,39 @@ size_t bls381_verify_batch_randomized_workspace_size(size_t n, size_t batch) {
 int bls381_verify_batch_randomized_device(size_t n, const uint8_t* d_pks, const uint8_t* d_msgs32,
                                           const uint8_t* d_sigs, const uint8_t* d_dom8s, const uint8_t seed[32],
                                           size_t batch, uint8_t* d_verdicts, void* d_workspace, void* stream,
-                                          uint64_t* stats) try {
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  if (n == 0) return 0;
-  if (!d_pks || !d_msgs32 || !d_sigs || !d_dom8s || !seed || !d_verdicts || !d_workspace || batch < 2 || batch % 2 ||
-      batch > RB_BATCH_MAX)
-    return BLS381_EARG;
-  return run_verify_randomized(c, n, d_pks, d_msgs32, d_sigs, d_dom8s, seed, batch, d_verdicts, d_workspace,
-                               rb_ws_size(n, batch), (hipStream_t)stream, stats);
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                          uint64_t* stats) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    if (n == 0) return 0;
+    if (!d_pks || !d_msgs32 || !d_sigs || !d_dom8s || !seed || !d_verdicts || !d_workspace || batch < 2 || batch % 2 ||
+        batch > RB_BATCH_MAX)
+      return BLS381_EARG;
+    return run_verify_randomized(c, n, d_pks, d_msgs32, d_sigs, d_dom8s, seed, batch, d_verdicts, d_workspace,
+                                 rb_ws_size(n, batch), (hipStream_t)stream, stats);
+  });
 }
 
 int bls381_verify_batch_randomized(size_t n, const uint8_t* pks, const uint8_t* msgs32, const uint8_t* sigs,
                                    const uint8_t* dom8s, const uint8_t seed[32], size_t batch,
-                                   uint8_t* verdicts_out) try {
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  if (n == 0) return 0;
-  if (!pks || !msgs32 || !sigs || !dom8s || !seed || !verdicts_out || batch < 2 || batch % 2 || batch > RB_BATCH_MAX)
-    return BLS381_EARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t in_bytes = align256(48 * n) + align256(32 * n) + align256(96 * n) + align256(8 * n) + align256(n);
-  const size_t wsb = rb_ws_size(n, batch);
-  if ((rc = ensure_ws(c, in_bytes + wsb + 1024))) return rc;
-  Bump b(c->ws, c->ws_cap);
-  uint8_t* d_pks = b.take<uint8_t>(48 * n);
-  uint8_t* d_msgs = b.take<uint8_t>(32 * n);
-  uint8_t* d_sigs = b.take<uint8_t>(96 * n);
-  uint8_t* d_doms = b.take<uint8_t>(8 * n);
-  uint8_t* d_v = b.take<uint8_t>(n);
-  void* ws = b.take<uint8_t>(wsb);
-  hipStream_t s = c->stream;
-  HIPC(hipMemcpyAsync(d_pks, pks, 48 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_msgs, msgs32, 32 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_sigs, sigs, 96 * n, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(d_doms, dom8s, 8 * n, hipMemcpyHostToDevice, s));
-  if ((rc = run_verify_randomized(c, n, d_pks, d_msgs, d_sigs, d_doms, seed, batch, d_v, ws, wsb, s, nullptr)))
-    return rc;
-  HIPC(hipMemcpyAsync(verdicts_out, d_v, n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return 0;
-} catch (const std::exception& e) {
-  t_err = e.what();
-  return BLS381_EARG;
+                                   uint8_t* verdicts_out) {
+  return guarded([&]() -> int {
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    if (n == 0) return 0;
+    if (!pks || !msgs32 || !sigs || !dom8s || !seed || !verdicts_out || batch < 2 || batch % 2 || batch > RB_BATCH_MAX)
+      return BLS381_EARG;
+    HostCall hc(c);
+    const size_t wsb = rb_ws_size(n, batch);
+    VerifyIn d;
+    TRY(hc.carve([&](Bump& b) { d.carve(b, n, wsb); }));
+    TRY(d.upload(hc, n, pks, msgs32, sigs, dom8s));
+    TRY(run_verify_randomized(c, n, d.pks, d.msgs, d.sigs, d.doms, seed, batch, d.v, d.ws, wsb, hc.s, nullptr));
+    TRY(hc.download(verdicts_out, d.v, n));
+    return hc.finish();
+  });
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Basic types and qualifiers shared by the gfx950 kernels and the host unit-test
 // build of the same arithmetic (DESIGN.md "One source, two compilers").
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIP__)
@@ -59,5 +60,19 @@ struct g1_jac { fp_t x, y, z; };
 struct g2_jac { fp2_t x, y, z; };
 struct g1_aff { fp_t x, y; };
 struct g2_aff { fp2_t x, y; };
+
+// ---- launch-layout constants the kernels share with the host planners (bls381_plan.hpp)
+constexpr int KBLOCK = 128;   // lanes per workgroup for the per-item kernels
+// A contiguous range [begin, end) of inputs belonging to one group (aggregation kernels,
+// segmented Fp12 products)
+struct agg_chunk { uint32_t begin, end; };
+// split Miller loop: line products per item of a chunk (layout: bls381_kernels.hpp "split Miller loop")
+constexpr int ML_STEPS = 68;   // 63 doubling + 5 addition steps over |x|
+constexpr int ML_LC = 5;
+constexpr size_t ML_L_WORDS_PER_ITEM = (size_t)ML_STEPS * ML_LC * FP_LIMBS * 2;
+// SSZ root programs (bls381_ssz.hpp)
+enum : uint32_t { SSZ_CHUNK = 1, SSZ_MERKLE = 2 };
+constexpr int SSZ_STACK = 64;    // chunks
+constexpr int SSZ_PROG_MAX = 512;  // u32 words
 
 }  // namespace bls381

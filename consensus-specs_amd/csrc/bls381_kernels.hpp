@@ -31,7 +31,7 @@ enum : int { CHK_SUB_MASK = 3, CHK_LAX = 4 };
 // the strict codec rejects it (k_reg_decode, agg_accumulate).
 constexpr uint8_t ST_NONCANON = 0x80;
 
-constexpr int KBLOCK = 128;   // lanes per workgroup for the per-item kernels
+// KBLOCK (lanes per workgroup for the per-item kernels): bls381_defs.hpp
 // minimum waves per SIMD requested from the register allocator for the heavy
 // per-item kernels (1 = up to 512 VGPR+AGPR per lane, 2 = up to 256).  Two:
 // one wave alone issues a VALU op every 4 cycles, a second fills the other 2.
@@ -436,52 +436,14 @@ __global__ void __launch_bounds__(KBLOCK) k_hash_search(size_t n, const uint8_t*
 }
 
 // --------------------------------------------------------- verify kernels --
-// One bls_verify per lane pair: FE( ML(sig, -g1) * ML(H(m), pk) ) == 1, with the
+// One bls_verify per item: FE( ML(sig, -g1) * ML(H(m), pk) ) == 1, with the
 // infinity short-circuit of py_ecc's pairing (a pair with an infinite point is 1).
-// sig_check (STRICT policy): the signature's G2 membership is tested here, on the loop's
+// sig_check (STRICT policy, k_ml_lines): the signature's G2 membership is tested on the loop's
 // final running point T = [|x|] sig (psi(sig) == -T), instead of by 64 more doublings in
 // k_decode_g2; a signature outside G2 makes the verdict False either way.
-__global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify(size_t n, const uint32_t* __restrict__ sig_aff,
-                                                         const uint8_t* __restrict__ sig_st,
-                                                         const uint32_t* __restrict__ pk_aff,
-                                                         const uint8_t* __restrict__ pk_st,
-                                                         const uint32_t* __restrict__ h_aff,
-                                                         uint32_t* __restrict__ f_out, uint8_t* __restrict__ st_out,
-                                                         int sig_check) {
-  const size_t i = item_index<2>();
-  if (i >= n) return;
-  const bool lead = !pr_odd();
-  const uint8_t ss = sig_st[i], ps = pk_st[i];
-  if (ss == ST_BAD || ps == ST_BAD) { if (lead) st_out[i] = ST_BAD; return; }
-  aff_t<fp2p_t> Q[2];
-  g1_line_pre P[2];
-  int np = 0;
-  if (ss == ST_OK) {
-    Q[np] = soa_ld_g2(sig_aff, n, i);
-    aff_t<fp_t> ng; ng.x = G1_VGEN_X_M; ng.y = G1_VGEN_NEGY_M;
-    P[np] = g1_prepare(ng);
-    ++np;
-  }
-  if (ps == ST_OK) {
-    Q[np] = soa_ld_g2(h_aff, n, i);
-    P[np] = g1_prepare(soa_ld_g1(pk_aff, n, i));
-    ++np;
-  }
-  fp12p_t f;
-  bool degen = false;
-  g2_proj<fp2p_t> T0;
-  g2_proj<fp2p_t>* t0 = (sig_check && ss == ST_OK) ? &T0 : nullptr;
-  if (np == 2) f = miller_loop_n<2>(Q, P, degen, t0);
-  else if (np == 1) f = miller_loop_n<1>(Q, P, degen, t0);
-  else f = fp12_one<fp2p_t>();
-  bool bad = degen;   // a degenerate loop is py_ecc's zero pairing value: verdict False
-  if (t0 && !degen) bad = !g2_psi_matches_neg(Q[0], T0);
-  soa_st12(f_out, n, i, f);
-  if (lead) st_out[i] = bad ? ST_BAD : ST_OK;
-}
 
 // ----------------------------------------- split Miller loop (throughput path) --
-// The two-pair Miller loop of k_miller_verify in two kernels, so that neither holds the
+// The two-pair Miller loop (miller_loop_n<2>) in two kernels, so that neither holds the
 // other's state (DESIGN.md §6 "Split Miller loop"):
 //   k_ml_lines   one item per lane quad.  The lo half runs the running point of the pair
 //                (sig, -[c]g1), the hi half that of (BP(H0), pk).  At each of the 68 Miller
@@ -495,9 +457,8 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify(s
 // L layout (per item i of a chunk of cnt items, step j, Fp2 component c, this lane's
 // coefficient p): limb k at L[((j * ML_LC + c) * 14 + k) * 2 cnt + 2 i + p], c = 0..2 the
 // w^0 half (L00, L01, L02), c = 3..4 (L11, L12) -- L10 is always zero.
-constexpr int ML_STEPS = 68;   // 63 doubling + 5 addition steps over |x|
-constexpr int ML_LC = 5;
-constexpr size_t ML_L_WORDS_PER_ITEM = (size_t)ML_STEPS * ML_LC * FP_LIMBS * 2;
+// (ML_STEPS = 68, 63 doubling + 5 addition steps over |x|, ML_LC = 5 and ML_L_WORDS_PER_ITEM:
+// bls381_defs.hpp)
 enum : uint8_t { ML_ST_ONE = 4 };   // both pairs infinite: the item's Miller value is 1
 
 // L = l l' of the lo half's line l = x (c0, c1, c2) and the hi half's l' (d0, d1, d2), on a quad:
@@ -896,7 +857,7 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_ml_accum_q(size
 
 // The same verify on a lane quad (bls381_quad.hpp): the lo half runs the pair
 // (sig, -g1), the hi half (H(m), pk), side by side; a single finite pair runs on
-// lo with the hi half idle.  f is stored in the layout of k_miller_verify (each
+// lo with the hi half idle.  f is stored in the lane-pair layout of k_ml_accum (each
 // half writes its three Fp2 components), so the final exponentiation is shared.
 __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_q(size_t n, const uint32_t* __restrict__ sig_aff,
                                                            const uint8_t* __restrict__ sig_st,
@@ -942,7 +903,7 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_q
   if (lead) st_out[i] = degen ? ST_BAD : ST_OK;
 }
 
-// The latency form of k_miller_verify: one quad per Miller pair (miller_loop_q1).
+// The latency form of the verify Miller stage: one quad per Miller pair (miller_loop_q1).
 // Pair task t = 2i + k of item i runs on lanes 4t..4t+3: k = 0 the pair
 // (sig, -[c]g1), k = 1 (BP(H0), pk).  Each task writes its own Fp12 (pair SoA over
 // 2n values) and status; an inactive pair (infinite operand) writes f = 1.
@@ -1468,8 +1429,7 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_rb_miller_sig(s
 // Each workgroup sums one chunk: item slots (one lane, or one lane pair for G2)
 // stride over the chunk, then a tree reduction of Jacobian partials staged in
 // LDS.  The input is either compressed points (level 1: decode + sum) or
-// Jacobian SoA partials.
-struct agg_chunk { uint32_t begin, end; };
+// Jacobian SoA partials.  (agg_chunk: bls381_defs.hpp)
 
 template <class F> struct pt_traits;
 template <> struct pt_traits<fp_t> {

@@ -16,9 +16,7 @@
 
 namespace bls381 {
 
-enum : uint32_t { SSZ_CHUNK = 1, SSZ_MERKLE = 2 };
-constexpr int SSZ_STACK = 64;    // chunks
-constexpr int SSZ_PROG_MAX = 512;  // u32 words
+// SSZ_CHUNK, SSZ_MERKLE, SSZ_STACK (chunks) and SSZ_PROG_MAX (u32 words): bls381_defs.hpp
 
 // SHA-256 of two 32-byte chunks (one data block + the constant padding block)
 BLS_DEV_INLINE void sha256_pair(uint32_t out[8], const uint32_t l[8], const uint32_t r[8]) {

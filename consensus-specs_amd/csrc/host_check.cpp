@@ -17,6 +17,7 @@
 
 #include "bls381_hash.hpp"
 #include "bls381_pairing.hpp"
+#include "bls381_plan.hpp"
 #include "bls381_ssz.hpp"
 
 using namespace bls381;
@@ -416,5 +417,92 @@ int hc_count_aggregate(size_t n, const uint8_t* pks, uint64_t* out) {
   return 0;
 }
 #endif
+
+// ---- host planners (bls381_plan.hpp), as flat arrays.  A writer returns the u32 words it
+// wrote, or -1 when `cap` words do not hold them.  A chunk-list sequence (product passes,
+// aggregation levels) is written as: count, then per list its length and begin/end pairs.
+}  // extern "C"
+namespace {
+struct Words {
+  uint32_t* out;
+  size_t cap, n = 0;
+  bool ok = true;
+  void put(uint64_t v) {
+    if (n < cap) out[n++] = (uint32_t)v; else ok = false;
+  }
+  template <class T> void vec(const std::vector<T>& v) {
+    put(v.size());
+    for (const T& x : v) put((uint32_t)x);
+  }
+  void lists(const std::vector<std::vector<agg_chunk>>& ls) {
+    put(ls.size());
+    for (const auto& l : ls) {
+      put(l.size());
+      for (const agg_chunk& c : l) { put(c.begin); put(c.end); }
+    }
+  }
+  long done() const { return ok ? (long)n : -1; }
+};
+// scalars (n_calls, n_keys, G, nquads, tasks, nslots, vm_ws_bound lo / hi), then every array of
+// the plan in declaration order, then the aggregation levels
+long dump_vm_plan(const VmPlan& pl, size_t mlen, uint32_t* out, size_t cap) {
+  Words w{out, cap};
+  const uint64_t bound = vm_ws_bound(pl, mlen);
+  for (uint64_t v : {(uint64_t)pl.n_calls, (uint64_t)pl.n_keys, (uint64_t)pl.G, (uint64_t)pl.nquads, (uint64_t)pl.tasks,
+                     (uint64_t)pl.nslots, bound & 0xffffffffu, bound >> 32})
+    w.put(v);
+  w.vec(pl.key_idx); w.vec(pl.group_off); w.vec(pl.group_msg); w.vec(pl.group_call); w.vec(pl.quad_pair);
+  w.vec(pl.call_quad_off); w.lists(pl.passes); w.lists(pl.task_passes); w.vec(pl.quad_slot); w.vec(pl.sig_slot);
+  w.vec(pl.sig_task); w.lists(pl.agg.levels);
+  return w.done();
+}
+}  // namespace
+extern "C" {
+
+long hc_plan_products(size_t nseg, const uint32_t* off, uint32_t* out, size_t cap) {
+  Words w{out, cap};
+  w.lists(plan_products(std::vector<uint32_t>(off, off + nseg + 1)));
+  return w.done();
+}
+
+// sizes[0] = agg_ws_size of the plan for points of ncomp Fp components, sizes[1] = the public G1
+// bound (3 components) for the same counts
+long hc_plan_agg(size_t ng, const uint32_t* offsets, int lanes_per_point, int ncomp, uint32_t* out, size_t cap,
+                 size_t sizes[2]) {
+  const AggPlan p = plan_agg(ng, offsets, lanes_per_point);
+  sizes[0] = agg_ws_size(p, ncomp);
+  sizes[1] = agg_ws_bound_sizes(ng, ng ? offsets[ng] - offsets[0] : 0);
+  Words w{out, cap};
+  w.lists(p.levels);
+  return w.done();
+}
+
+long hc_plan_vm(size_t n_calls, const uint32_t* call_off, const uint8_t* msgs, size_t mlen, const uint8_t* h_pks,
+                const uint8_t* h_sigs, const int* with_sig, uint32_t* out, size_t cap) {
+  return dump_vm_plan(plan_vm(n_calls, call_off, msgs, mlen, h_pks, h_sigs, with_sig), mlen, out, cap);
+}
+
+long hc_plan_vm_grouped(size_t n_calls, const uint32_t* call_group_off, const uint32_t* group_key_off,
+                        const uint8_t* msgs, size_t mlen, uint32_t* out, size_t cap) {
+  return dump_vm_plan(plan_vm_grouped(n_calls, call_group_off, group_key_off, msgs, mlen), mlen, out, cap);
+}
+
+// out[0] = the verify_multiple bound from sizes alone; out[1] = verify_ws_size(n_verify), out[2] =
+// the bytes carve_verify consumes for the same n
+void hc_vm_ws_bounds(size_t n_calls, size_t n_keys, size_t mlen, size_t n_verify, size_t out[3]) {
+  out[0] = vm_ws_bound_sizes(n_calls, n_keys, mlen);
+  out[1] = verify_ws_size(n_verify);
+  Bump count;
+  carve_verify(count, n_verify);
+  out[2] = count.off;
+}
+
+int hc_ssz_prog_ok(const uint32_t* prog, uint32_t plen, size_t item_size) { return ssz_prog_ok(prog, plen, item_size); }
+// the deposit signing program (SSZ_PROG_MAX words at most); *item_size = the DepositData bytes
+uint32_t hc_deposit_prog(uint32_t* out, size_t* item_size) {
+  std::memcpy(out, DEPOSIT_SIGNING_PROG, sizeof(DEPOSIT_SIGNING_PROG));
+  *item_size = DEPOSIT_DATA_BYTES;
+  return DEPOSIT_SIGNING_PROG_LEN;
+}
 
 }  // extern "C"
