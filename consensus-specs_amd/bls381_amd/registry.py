@@ -19,6 +19,27 @@ import numpy as np
 from . import _native
 
 
+DEPOSIT_BYTES = 1208     # BLS381_DEPOSIT_BYTES: 32 x 32 B of proof, then the 184 B DepositData
+DEPOSIT_SKIPPED, DEPOSIT_NEW, DEPOSIT_TOPUP = 0, 1, 2   # BLS381_DEPOSIT_*
+
+
+class DepositResult:
+    """What process_deposit did with each deposit of a batch (include/bls381.h
+    bls381_registry_process_deposits): ``outcome[i]`` (DEPOSIT_*), ``validator_index[i]`` (the
+    entry holding the key, -1 when skipped), ``first_bad_proof`` (the first deposit whose Merkle
+    branch fails, the spec's assert, or -1) and ``n_new`` (deposits that register a validator)."""
+
+    def __init__(self, outcome, validator_index, first_bad_proof, n_new):
+        self.outcome = outcome
+        self.validator_index = validator_index
+        self.first_bad_proof = first_bad_proof
+        self.n_new = n_new
+
+    def __repr__(self):
+        return "DepositResult(n=%d, n_new=%d, first_bad_proof=%d)" % (len(self.outcome), self.n_new,
+                                                                      self.first_bad_proof)
+
+
 class PubkeyRegistry:
     """Append-only table of decoded pubkeys on the current device.
 
@@ -65,6 +86,29 @@ class PubkeyRegistry:
             _native.check(_native.lib().bls381_registry_lookup(self._h, n, blob,
                                                                out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+    def process_deposits(self, deposits, first_index: int, deposit_root: bytes, domain: int,
+                         commit: bool = True) -> DepositResult:
+        """process_deposit (0_beacon-chain.md:1732-1775) on serialized Deposits (ssz.Deposit, 1,208
+        bytes each) in order, ``state.deposit_index`` starting at ``first_index``, with this
+        registry as the validator pubkeys.  With ``commit`` and every proof good, the new
+        validators' keys are appended in deposit order.  A failing proof leaves the registry
+        untouched and is reported in ``first_bad_proof`` (the caller raises the spec's assert)."""
+        blob = b"".join(bytes(d) for d in deposits)
+        n = len(blob) // DEPOSIT_BYTES
+        if n * DEPOSIT_BYTES != len(blob):
+            raise ValueError("Deposit serializations are %d bytes" % DEPOSIT_BYTES)
+        root = bytes(deposit_root)
+        if len(root) != 32:
+            raise ValueError("deposit_root must be 32 bytes")
+        outcome = np.zeros(n, dtype=np.uint8)
+        vidx = np.full(n, -1, dtype=np.int32)
+        bad = ctypes.c_int64(-1)
+        if n:
+            _native.check(_native.lib().bls381_registry_process_deposits(
+                self._h, n, blob, int(first_index), root, int(domain).to_bytes(8, "big"), int(bool(commit)),
+                outcome.ctypes.data_as(ctypes.c_void_p), vidx.ctypes.data_as(ctypes.c_void_p), ctypes.byref(bad)))
+        return DepositResult(outcome, vidx, int(bad.value), int(np.count_nonzero(outcome == DEPOSIT_NEW)))
 
     def aggregate_indices(self, groups) -> list:
         """bls_aggregate_pubkeys over registry entries, one result per group (list of index lists)."""

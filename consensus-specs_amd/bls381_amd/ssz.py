@@ -9,8 +9,13 @@ Here a fixed-size type compiles into a short program over the item's SSZ
 serialization (csrc/bls381_ssz.hpp), and the engine runs it for a whole batch,
 one lane per item.  The bytes equal ssz_impl's for the same values.
 
-Types: ``uint(nbytes)``, ``BOOL``, ``Bytes(n)``, ``Container((name, type), ...)``;
-the beacon-chain containers on the BLS path are predefined below.
+Types: ``uint(nbytes)``, ``BOOL``, ``Bytes(n)``, ``Vector(type, n)``,
+``Container((name, type), ...)``; the beacon-chain containers on the BLS path are
+predefined below.
+
+``verify_merkle_branch_batch`` runs the spec's verify_merkle_branch
+(0_beacon-chain.md:846-857) for a batch; the whole of process_deposit is
+``registry.PubkeyRegistry.process_deposits``.
 """
 from __future__ import annotations
 
@@ -35,6 +40,10 @@ def Bytes(n: int):
     return ("bytes", n)
 
 
+def Vector(elem, n: int):
+    return ("vector", elem, n)
+
+
 def Container(*fields):
     return ("container", list(fields))
 
@@ -48,6 +57,7 @@ AttestationData = Container(("beacon_block_root", Bytes(32)), ("source_epoch", u
 AttestationDataAndCustodyBit = Container(("data", AttestationData), ("custody_bit", BOOL))
 DepositData = Container(("pubkey", Bytes(48)), ("withdrawal_credentials", Bytes(32)), ("amount", uint(8)),
                         ("signature", Bytes(96)))
+Deposit = Container(("proof", Vector(Bytes(32), 32)), ("data", DepositData))
 BeaconBlockHeader = Container(("slot", uint(8)), ("parent_root", Bytes(32)), ("state_root", Bytes(32)),
                               ("body_root", Bytes(32)), ("signature", Bytes(96)))
 
@@ -60,6 +70,8 @@ def item_size(typ) -> int:
         return 1
     if k == "bytes":
         return typ[1]
+    if k == "vector":
+        return typ[2] * item_size(typ[1])
     return sum(item_size(t) for _, t in typ[1])
 
 
@@ -75,6 +87,11 @@ def serialize(typ, v) -> bytes:
         if len(v) != typ[1]:
             raise ValueError("expected %d bytes" % typ[1])
         return v
+    if k == "vector":
+        v = list(v)
+        if len(v) != typ[2]:
+            raise ValueError("expected %d elements" % typ[2])
+        return b"".join(serialize(typ[1], x) for x in v)
     return b"".join(serialize(t, v[name]) for name, t in typ[1])
 
 
@@ -92,6 +109,14 @@ def _emit(typ, off: int, prog: list) -> int:
         if pieces > 1:
             prog += [SSZ_MERKLE, pieces]
         return off + n
+    if k == "vector":
+        if typ[1][0] in ("uint", "bool"):
+            # basic elements are packed (ssz_impl.py:110-123): the chunks of the serialization
+            return _emit(Bytes(item_size(typ)), off, prog)
+        for _ in range(typ[2]):
+            off = _emit(typ[1], off, prog)
+        prog += [SSZ_MERKLE, typ[2]]
+        return off
     for _, t in typ[1]:
         off = _emit(t, off, prog)
     prog += [SSZ_MERKLE, len(typ[1])]
@@ -150,4 +175,27 @@ def verify_deposits(deposit_datas, domain) -> np.ndarray:
     if n:
         dom = int(domain).to_bytes(8, "big") * n
         _native.check(_native.lib().bls381_verify_deposits(n, blob, dom, out.ctypes.data_as(ctypes.c_void_p)))
+    return out.astype(bool)
+
+
+def verify_merkle_branch_batch(leaves, proofs, depth: int, indices, root_or_roots) -> np.ndarray:
+    """verify_merkle_branch (0_beacon-chain.md:846-857) per item: ``leaves[i]`` (32 bytes) with the
+    ``depth`` siblings ``proofs[i]`` (a sequence of 32-byte values, or their concatenation) under
+    ``indices[i]`` against one 32-byte root, or against ``root_or_roots[i]``."""
+    leaves = [bytes(x) for x in leaves]
+    n = len(leaves)
+    depth = int(depth)
+    flat = [bytes(p) if isinstance(p, (bytes, bytearray, memoryview)) else b"".join(bytes(s) for s in p)
+            for p in proofs]
+    single = isinstance(root_or_roots, (bytes, bytearray, memoryview))
+    roots = [bytes(root_or_roots)] if single else [bytes(r) for r in root_or_roots]
+    idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+    if (any(len(x) != 32 for x in leaves) or any(len(r) != 32 for r in roots) or len(flat) != n or len(idx) != n
+            or any(len(p) != 32 * depth for p in flat) or (not single and len(roots) != n)):
+        raise ValueError("verify_merkle_branch_batch: 32-byte leaves and roots, depth siblings and one index per item")
+    out = np.zeros(n, dtype=np.uint8)
+    # depth and the stride are checked by the engine (BLS381_EARG -> ValueError)
+    _native.check(_native.lib().bls381_merkle_branch_batch(
+        n, b"".join(leaves) or None, b"".join(flat) or None, depth, idx.ctypes.data_as(ctypes.c_void_p) if n else None,
+        b"".join(roots) or None, 0 if single else 32, out.ctypes.data_as(ctypes.c_void_p) if n else None))
     return out.astype(bool)

@@ -1823,6 +1823,216 @@ int bls381_verify_deposits(size_t n, const uint8_t* deposit_data, const uint8_t*
   });
 }
 
+// ---- verify_merkle_branch batches and process_deposit over the registry
+static bool merkle_args_ok(size_t n, const void* leaves, const void* proofs, uint32_t depth, const void* indices,
+                           const void* roots, size_t root_stride, const void* ok_out) {
+  if (depth > 64 || (root_stride != 0 && root_stride != 32) || n > (size_t)INT32_MAX) return false;
+  return n == 0 || (leaves && (proofs || depth == 0) && indices && roots && ok_out);
+}
+
+int bls381_merkle_branch_batch_device(size_t n, const uint8_t* d_leaves32, const uint8_t* d_proofs, uint32_t depth,
+                                      const uint64_t* d_indices, const uint8_t* d_roots32, size_t root_stride,
+                                      uint8_t* d_ok, void* stream) {
+  return guarded([&]() -> int {
+    if (!merkle_args_ok(n, d_leaves32, d_proofs, depth, d_indices, d_roots32, root_stride, d_ok)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    LAUNCH("merkle_branch", (hipStream_t)stream, dim3(grid_for(n)), dim3(KBLOCK), k_merkle_branch, n, d_leaves32,
+           d_proofs, (size_t)32 * depth, depth, d_indices, (uint64_t)0, d_roots32, root_stride, d_ok,
+           (uint32_t*)nullptr);
+    return 0;
+  });
+}
+
+int bls381_merkle_branch_batch(size_t n, const uint8_t* leaves32, const uint8_t* proofs, uint32_t depth,
+                               const uint64_t* indices, const uint8_t* roots32, size_t root_stride, uint8_t* ok_out) {
+  return guarded([&]() -> int {
+    if (!merkle_args_ok(n, leaves32, proofs, depth, indices, roots32, root_stride, ok_out)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t proof_bytes = (size_t)32 * depth * n, root_bytes = root_stride ? 32 * n : 32;
+    uint8_t *d_leaves, *d_proofs, *d_roots, *d_ok;
+    uint64_t* d_idx;
+    TRY(hc.carve([&](Bump& b) {
+      d_leaves = b.take<uint8_t>(32 * n);
+      d_proofs = b.take<uint8_t>(proof_bytes + 1);
+      d_idx = b.take<uint64_t>(n);
+      d_roots = b.take<uint8_t>(root_bytes);
+      d_ok = b.take<uint8_t>(n);
+    }));
+    TRY(hc.upload(d_leaves, leaves32, 32 * n));
+    TRY(hc.upload(d_proofs, proofs, proof_bytes));
+    TRY(hc.upload(d_idx, indices, 8 * n));
+    TRY(hc.upload(d_roots, roots32, root_bytes));
+    TRY(bls381_merkle_branch_batch_device(n, d_leaves, d_proofs, depth, d_idx, d_roots, root_stride, d_ok, hc.s));
+    TRY(hc.download(ok_out, d_ok, n));
+    return hc.finish();
+  });
+}
+
+static_assert(BLS381_DEPOSIT_SKIPPED == DEP_SKIPPED && BLS381_DEPOSIT_NEW == DEP_NEW &&
+                  BLS381_DEPOSIT_TOPUP == DEP_TOPUP && BLS381_DEPOSIT_BYTES == DEPOSIT_BYTES,
+              "include/bls381.h and the kernels agree on the deposit constants");
+
+// process_deposits' workspace: the gathered keys and signatures, the leaves and the signing roots,
+// the replicated domain, the per-deposit verdicts / registry entries / winners, the batch-local key
+// table, {first bad proof, NEW count}, the deposit root and the domain, and the root program's and
+// the verify batch's own
+struct ProcessDepositsWs {
+  uint8_t *pks, *sigs, *leaves, *sroots, *doms, *verdicts, *proof_ok, *consts;
+  int32_t *entry, *win;
+  uint32_t *table, *meta;
+  size_t slots;
+  SszWs ssz;
+  void* verify;
+};
+static ProcessDepositsWs carve_process_deposits(Bump& b, size_t n) {
+  ProcessDepositsWs w;
+  w.pks = b.take<uint8_t>(48 * n);
+  w.sigs = b.take<uint8_t>(96 * n);
+  w.leaves = b.take<uint8_t>(32 * n);
+  w.sroots = b.take<uint8_t>(32 * n);
+  w.doms = b.take<uint8_t>(8 * n);
+  w.verdicts = b.take<uint8_t>(n);
+  w.proof_ok = b.take<uint8_t>(n);
+  w.consts = b.take<uint8_t>(40);
+  w.entry = b.take<int32_t>(n);
+  w.win = b.take<int32_t>(n);
+  w.slots = deposit_table_slots(n);
+  w.table = b.take<uint32_t>(w.slots);
+  w.meta = b.take<uint32_t>(2);
+  w.ssz = carve_ssz(b);
+  w.verify = b.take<uint8_t>(verify_ws_size(n));
+  return w;
+}
+size_t bls381_registry_process_deposits_workspace_size(size_t n) {
+  return carved_bytes([&](Bump& b) { carve_process_deposits(b, n); });
+}
+
+// Both forms, with reg->mu held: everything on `s`, synchronised before the registry's size moves.
+static int process_deposits_impl(Ctx* c, bls381_registry* reg, size_t n, const uint8_t* d_deposits,
+                                 uint64_t first_index, const uint8_t* deposit_root, const uint8_t* dom8, int commit,
+                                 uint8_t* d_outcome, int32_t* d_vidx, int64_t* first_bad_proof, void* ws,
+                                 hipStream_t s) {
+  Bump b(ws, bls381_registry_process_deposits_workspace_size(n));
+  const ProcessDepositsWs w = carve_process_deposits(b, n);
+  const dim3 g(grid_for(n)), blk(KBLOCK);
+  const uint32_t mask = (uint32_t)(w.slots - 1);
+  auto consts = std::make_shared<std::vector<uint8_t>>(40);
+  std::memcpy(consts->data(), deposit_root, 32);
+  std::memcpy(consts->data() + 32, dom8, 8);
+  HIPC(hipMemcpyAsync(w.consts, consts->data(), 40, hipMemcpyHostToDevice, s));
+  TRY(keep_until_done(c, s, consts));
+  HIPC(hipMemsetAsync(w.table, 0xFF, 4 * w.slots, s));
+  HIPC(hipMemsetAsync(w.meta, 0xFF, 8, s));
+  const uint8_t* d_data = d_deposits + DEPOSIT_PROOF_BYTES;
+  LAUNCH("gather_pubkeys", s, dim3(grid_for(48 * n)), blk, k_gather_field, n, d_data, DEPOSIT_BYTES, 0u, 48u, w.pks);
+  LAUNCH("gather_signatures", s, dim3(grid_for(96 * n)), blk, k_gather_field, n, d_data, DEPOSIT_BYTES, 88u, 96u,
+         w.sigs);
+  LAUNCH("gather_domain", s, dim3(grid_for(8 * n)), blk, k_gather_field, n, (const uint8_t*)w.consts, (size_t)0, 32u,
+         8u, w.doms);
+  // the spec's assert: the leaf hash_tree_root(deposit.data) under index first_index + i
+  TRY(ssz_root_impl(n, d_data, DEPOSIT_BYTES, DEPOSIT_ROOT_PROG, DEPOSIT_ROOT_PROG_LEN, w.leaves, w.ssz, s, c));
+  LAUNCH("merkle_branch", s, g, blk, k_merkle_branch, n, (const uint8_t*)w.leaves, d_deposits, DEPOSIT_BYTES,
+         DEPOSIT_PROOF_DEPTH, (const uint64_t*)nullptr, first_index, (const uint8_t*)w.consts, (size_t)0, w.proof_ok,
+         w.meta);
+  // pubkey in validator_pubkeys, then the proof of possession of every deposit
+  LAUNCH("registry_lookup", s, g, blk, k_reg_lookup, n, (const uint8_t*)w.pks, (const uint8_t*)reg->keys,
+         (const uint32_t*)reg->table, reg->tmask, w.entry);
+  TRY(ssz_root_impl(n, d_data, DEPOSIT_BYTES, DEPOSIT_SIGNING_PROG, DEPOSIT_SIGNING_PROG_LEN, w.sroots, w.ssz, s, c));
+  TRY(run_verify_batch(c, n, w.pks, w.sroots, w.sigs, w.doms, w.verdicts, w.verify, s));
+  // the in-order rule
+  LAUNCH("deposit_insert", s, g, blk, k_deposit_insert, n, (const uint8_t*)w.pks, (const int32_t*)w.entry,
+         (const uint8_t*)w.verdicts, w.table, mask);
+  LAUNCH("deposit_resolve", s, g, blk, k_deposit_resolve, n, (const uint8_t*)w.pks, (const int32_t*)w.entry,
+         (const uint32_t*)w.table, mask, d_outcome, w.win);
+  LAUNCH("deposit_scan", s, dim3(1), blk, k_deposit_scan, n, (uint32_t)reg->size, (const uint8_t*)d_outcome,
+         (const int32_t*)w.entry, (const int32_t*)w.win, d_vidx, w.meta + 1);
+  uint32_t meta[2];
+  HIPC(hipMemcpyAsync(meta, w.meta, 8, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  *first_bad_proof = meta[0] == REG_EMPTY ? -1 : (int64_t)meta[0];
+  const size_t n_new = meta[1];
+  if (*first_bad_proof >= 0) return 0;
+  if (!commit || n_new == 0) return (int)n_new;
+  if (reg->size + n_new > reg->cap) { t_err = "registry capacity exceeded"; return BLS381_EARG; }
+  const size_t first = reg->size;
+  LAUNCH("deposit_compact", s, g, blk, k_deposit_compact, n, (const uint8_t*)w.pks, (const uint8_t*)d_outcome,
+         (const int32_t*)d_vidx, reg->cap, reg->keys);
+  LAUNCH("registry_decode", s, dim3(grid_for(n_new)), blk, k_reg_decode, first, n_new, reg->cap,
+         (const uint8_t*)reg->keys, reg->aff, reg->st);
+  LAUNCH("registry_insert", s, dim3(grid_for(n_new)), blk, k_reg_insert, first, n_new, (const uint8_t*)reg->keys,
+         (const uint8_t*)reg->st, reg->table, reg->tmask);
+  HIPC(hipStreamSynchronize(s));
+  reg->size += n_new;
+  return (int)n_new;
+}
+
+static bool process_deposits_args_ok(const bls381_registry* reg, size_t n, const void* deposits,
+                                     const uint8_t* deposit_root, const uint8_t* dom8, const void* outcome,
+                                     const void* vidx, const int64_t* first_bad_proof) {
+  if (!reg || !first_bad_proof || n > (size_t)INT32_MAX / 2) return false;
+  return n == 0 || (deposits && deposit_root && dom8 && outcome && vidx);
+}
+
+int bls381_registry_process_deposits_device(bls381_registry* reg, size_t n, const uint8_t* d_deposits,
+                                            uint64_t first_index, const uint8_t deposit_root[32],
+                                            const uint8_t dom8[8], int commit, uint8_t* d_outcome,
+                                            int32_t* d_validator_index, int64_t* first_bad_proof, void* d_workspace,
+                                            void* stream) {
+  return guarded([&]() -> int {
+    if (!process_deposits_args_ok(reg, n, d_deposits, deposit_root, dom8, d_outcome, d_validator_index,
+                                  first_bad_proof) || (n && !d_workspace))
+      return BLS381_EARG;
+    *first_bad_proof = -1;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = registry_ctx(reg, &rc);
+    if (!c) return rc;
+    std::lock_guard<std::mutex> lr(reg->mu);
+    return process_deposits_impl(c, reg, n, d_deposits, first_index, deposit_root, dom8, commit, d_outcome,
+                                 d_validator_index, first_bad_proof, d_workspace, (hipStream_t)stream);
+  });
+}
+
+int bls381_registry_process_deposits(bls381_registry* reg, size_t n, const uint8_t* deposits, uint64_t first_index,
+                                     const uint8_t deposit_root[32], const uint8_t dom8[8], int commit,
+                                     uint8_t* outcome, int32_t* validator_index, int64_t* first_bad_proof) {
+  return guarded([&]() -> int {
+    if (!process_deposits_args_ok(reg, n, deposits, deposit_root, dom8, outcome, validator_index, first_bad_proof))
+      return BLS381_EARG;
+    *first_bad_proof = -1;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = registry_ctx(reg, &rc);
+    if (!c) return rc;
+    std::lock_guard<std::mutex> lr(reg->mu);
+    HostCall hc(c);
+    const size_t wsb = bls381_registry_process_deposits_workspace_size(n);
+    uint8_t *d_dep, *d_out, *d_ws;
+    int32_t* d_vi;
+    TRY(hc.carve([&](Bump& b) {
+      d_dep = b.take<uint8_t>(DEPOSIT_BYTES * n);
+      d_out = b.take<uint8_t>(n);
+      d_vi = b.take<int32_t>(n);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_dep, deposits, DEPOSIT_BYTES * n));
+    const int n_new = process_deposits_impl(c, reg, n, d_dep, first_index, deposit_root, dom8, commit, d_out, d_vi,
+                                            first_bad_proof, d_ws, hc.s);
+    if (n_new < 0) return n_new;
+    TRY(hc.download(outcome, d_out, n));
+    TRY(hc.download(validator_index, d_vi, 4 * n));
+    TRY(hc.finish());
+    return n_new;
+  });
+}
+
 }  // extern "C"
 
 // ---- multi-GPU over RCCL: one process per GPU, a communicator

@@ -1725,6 +1725,134 @@ __global__ void __launch_bounds__(KBLOCK) k_gather_field(size_t n, const uint8_t
   out[t] = items[i * stride + off + b];
 }
 
+// ------------------------------------- Merkle branches and process_deposit --
+typedef __attribute__((address_space(1))) const uint8_t g_cu8;
+__device__ __forceinline__ uint32_t g_be32(g_cu8* p) {
+  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+}
+
+// verify_merkle_branch (0_beacon-chain.md:846-857) of n items, one lane each: leaf i at leaves + 32 i,
+// its `depth` siblings at proofs + i proof_stride, its index indices[i] (or index_base + i when
+// indices is null), its root at roots + i root_stride.  ok[i] = 1/0; first_bad (may be null)
+// receives the smallest failing i (the caller presets it to REG_EMPTY).
+__global__ void __launch_bounds__(KBLOCK) k_merkle_branch(size_t n, const uint8_t* __restrict__ leaves,
+                                                          const uint8_t* __restrict__ proofs, size_t proof_stride,
+                                                          uint32_t depth, const uint64_t* __restrict__ indices,
+                                                          uint64_t index_base, const uint8_t* __restrict__ roots,
+                                                          size_t root_stride, uint8_t* __restrict__ ok,
+                                                          uint32_t* first_bad) {
+  const size_t i = item_index<1>();
+  if (i >= n) return;
+  g_cu8* leaf = (g_cu8*)(leaves + 32 * i);
+  uint32_t v[8];
+  for (int w = 0; w < 8; ++w) v[w] = g_be32(leaf + 4 * w);
+  merkle_branch_root(v, (g_cu8*)(proofs + i * proof_stride), depth, indices ? indices[i] : index_base + i);
+  g_cu8* root = (g_cu8*)(roots + i * root_stride);
+  uint32_t d = 0;
+  for (int w = 0; w < 8; ++w) d |= v[w] ^ g_be32(root + 4 * w);
+  ok[i] = d == 0;
+  if (d != 0 && first_bad) atomicMin(first_bad, (uint32_t)i);
+}
+
+// outcomes of process_deposit (include/bls381.h BLS381_DEPOSIT_*)
+constexpr uint8_t DEP_SKIPPED = 0, DEP_NEW = 1, DEP_TOPUP = 2;
+
+// The batch-local key table of process_deposits (the registry's layout: REG_EMPTY when free,
+// linear probing, at least 2 n slots): deposit t enters it when its key is not registered
+// (entry[t] < 0) and its proof of possession holds.  Equal keys share a slot, which ends up
+// holding the smallest of their deposit indices (atomicMin, as k_reg_insert).
+__global__ void __launch_bounds__(KBLOCK) k_deposit_insert(size_t n, const uint8_t* __restrict__ keys,
+                                                           const int32_t* __restrict__ entry,
+                                                           const uint8_t* __restrict__ verdicts, uint32_t* table,
+                                                           uint32_t mask) {
+  const size_t t = item_index<1>();
+  if (t >= n) return;
+  if (entry[t] >= 0 || !verdicts[t]) return;
+  const uint32_t j = (uint32_t)t;
+  const uint8_t* k = keys + 48 * t;
+  uint32_t slot = reg_hash(k) & mask;
+  for (uint32_t probe = 0; probe <= mask; ++probe, slot = (slot + 1) & mask) {
+    uint32_t cur = __atomic_load_n(&table[slot], __ATOMIC_RELAXED);
+    if (cur == REG_EMPTY) {
+      cur = atomicCAS(&table[slot], REG_EMPTY, j);
+      if (cur == REG_EMPTY) return;
+    }
+    if (reg_key_eq(keys + 48 * (size_t)cur, k)) { atomicMin(&table[slot], j); return; }
+  }
+}
+
+// Once the table has settled: deposit t of a registered key is a top-up; otherwise the winner w
+// of its key's slot decides -- w == t: the deposit that registers the key; w < t: a top-up of
+// that deposit's validator (win[t] = w); no winner, or w > t (the key is registered only later
+// in the batch): the spec's early return.
+__global__ void __launch_bounds__(KBLOCK) k_deposit_resolve(size_t n, const uint8_t* __restrict__ keys,
+                                                            const int32_t* __restrict__ entry,
+                                                            const uint32_t* __restrict__ table, uint32_t mask,
+                                                            uint8_t* __restrict__ outcome, int32_t* __restrict__ win) {
+  const size_t t = item_index<1>();
+  if (t >= n) return;
+  if (entry[t] >= 0) { outcome[t] = DEP_TOPUP; win[t] = -1; return; }
+  const uint8_t* k = keys + 48 * t;
+  uint32_t slot = reg_hash(k) & mask;
+  uint32_t w = REG_EMPTY;
+  for (uint32_t probe = 0; probe <= mask; ++probe, slot = (slot + 1) & mask) {
+    const uint32_t cur = table[slot];
+    if (cur == REG_EMPTY) break;
+    if (reg_key_eq(keys + 48 * (size_t)cur, k)) { w = cur; break; }
+  }
+  const uint8_t oc = w == REG_EMPTY || w > (uint32_t)t ? DEP_SKIPPED : (w == (uint32_t)t ? DEP_NEW : DEP_TOPUP);
+  outcome[t] = oc;
+  win[t] = oc == DEP_TOPUP ? (int32_t)w : -1;
+}
+
+// Validator indices, by ONE workgroup: an exclusive scan of the NEW flags in deposit order gives
+// NEW deposit t the entry size_before + (NEW deposits before t); then every top-up of a key
+// registered in this batch takes its winner's entry.  *count_out = the number of NEW deposits.
+__global__ void __launch_bounds__(KBLOCK) k_deposit_scan(size_t n, uint32_t size_before,
+                                                         const uint8_t* __restrict__ outcome,
+                                                         const int32_t* __restrict__ entry,
+                                                         const int32_t* __restrict__ win, int32_t* vidx,
+                                                         uint32_t* __restrict__ count_out) {
+  __shared__ uint32_t sc[KBLOCK];
+  const uint32_t lane = threadIdx.x;
+  uint32_t base = 0;
+  for (size_t t0 = 0; t0 < n; t0 += KBLOCK) {
+    const size_t t = t0 + lane;
+    const uint8_t oc = t < n ? outcome[t] : DEP_SKIPPED;
+    const uint32_t is_new = oc == DEP_NEW ? 1u : 0u;
+    sc[lane] = is_new;
+    __syncthreads();
+    for (uint32_t d = 1; d < KBLOCK; d <<= 1) {
+      const uint32_t add = lane >= d ? sc[lane - d] : 0u;
+      __syncthreads();
+      sc[lane] += add;
+      __syncthreads();
+    }
+    if (t < n) vidx[t] = is_new ? (int32_t)(size_before + base + sc[lane] - 1) : (oc == DEP_TOPUP ? entry[t] : -1);
+    base += sc[KBLOCK - 1];
+    __syncthreads();
+  }
+  // one workgroup: the barrier orders the first pass's stores to vidx before the loads below, and
+  // a winner is a NEW deposit, whose entry the second pass never writes
+  __threadfence();
+  __syncthreads();
+  for (size_t t = lane; t < n; t += KBLOCK)
+    if (outcome[t] == DEP_TOPUP && entry[t] < 0) vidx[t] = vidx[win[t]];
+  if (lane == 0) *count_out = base;
+}
+
+// the NEW deposits' keys to their registry entries (keys + 48 vidx), in deposit order
+__global__ void __launch_bounds__(KBLOCK) k_deposit_compact(size_t n, const uint8_t* __restrict__ pks,
+                                                            const uint8_t* __restrict__ outcome,
+                                                            const int32_t* __restrict__ vidx, size_t cap,
+                                                            uint8_t* __restrict__ keys) {
+  const size_t t = item_index<1>();
+  if (t >= n || outcome[t] != DEP_NEW) return;
+  const size_t e = (size_t)vidx[t];
+  if (e >= cap) return;
+  for (int b = 0; b < 48; ++b) keys[48 * e + b] = pks[48 * t + b];
+}
+
 // ------------------------------------------------------- sign / privtopub --
 __device__ __forceinline__ scalar_t scalar_from_be32(const uint8_t* b) {
   scalar_t k;

@@ -492,5 +492,22 @@ constexpr uint32_t DEPOSIT_SIGNING_PROG[] = {SSZ_CHUNK, 0, 32, SSZ_CHUNK, 32, 16
                                              SSZ_CHUNK, 48, 32, SSZ_CHUNK, 80, 8, SSZ_MERKLE, 3};
 constexpr uint32_t DEPOSIT_SIGNING_PROG_LEN = sizeof(DEPOSIT_SIGNING_PROG) / 4;
 constexpr size_t DEPOSIT_DATA_BYTES = 48 + 32 + 8 + 96;
+// hash_tree_root(DepositData), the leaf of the deposit tree (0_beacon-chain.md:1742-1748): the four
+// fields, the signature Bytes96 as 3 chunks padded to 4
+constexpr uint32_t DEPOSIT_ROOT_PROG[] = {SSZ_CHUNK, 0, 32, SSZ_CHUNK, 32, 16, SSZ_MERKLE, 2,
+                                          SSZ_CHUNK, 48, 32, SSZ_CHUNK, 80, 8,
+                                          SSZ_CHUNK, 88, 32, SSZ_CHUNK, 120, 32, SSZ_CHUNK, 152, 32, SSZ_MERKLE, 3,
+                                          SSZ_MERKLE, 4};
+constexpr uint32_t DEPOSIT_ROOT_PROG_LEN = sizeof(DEPOSIT_ROOT_PROG) / 4;
+// a serialized Deposit (0_beacon-chain.md:457-461): the proof, Vector[Bytes32, 32], then the data
+constexpr uint32_t DEPOSIT_PROOF_DEPTH = 32;
+constexpr size_t DEPOSIT_PROOF_BYTES = 32 * DEPOSIT_PROOF_DEPTH;
+constexpr size_t DEPOSIT_BYTES = DEPOSIT_PROOF_BYTES + DEPOSIT_DATA_BYTES;
+// slots of process_deposits' batch-local key table: a power of two >= 2 n
+inline size_t deposit_table_slots(size_t n) {
+  size_t t = 16;
+  while (t < 2 * n) t <<= 1;
+  return t;
+}
 
 }  // namespace bls381

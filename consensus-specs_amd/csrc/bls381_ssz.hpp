@@ -11,6 +11,7 @@
 //   SSZ_MERKLE k      : pop k chunks, pad with zero chunks to a power of two,
 //                       merkleize, push the root
 // One lane runs the program for one item; the chunk stack lives in scratch.
+// merkle_branch_root folds a Merkle proof into a leaf (the spec's verify_merkle_branch).
 #pragma once
 #include "bls381_hash.hpp"
 
@@ -72,6 +73,26 @@ BLS_DEV_INLINE bool ssz_run(uint32_t root[8], const uint8_t* item, const uint32_
   if (sp != 1) return false;
   for (int w = 0; w < 8; ++w) root[w] = stk[0][w];
   return true;
+}
+
+// The fold of verify_merkle_branch (specs/core/0_beacon-chain.md:846-857): v holds the leaf
+// (8 big-endian words) and is left holding the root of the branch; sibling i is the 32 bytes
+// at proof + 32 i, and bit i of `index` puts it on the left (set) or on the right (clear).
+// depth <= 64.  P is a byte pointer: a global-address-space one on the device.
+template <class P>
+BLS_DEV_INLINE void merkle_branch_root(uint32_t v[8], P proof, uint32_t depth, uint64_t index) {
+  for (uint32_t i = 0; i < depth; ++i) {
+    const bool sib_left = (index >> i) & 1;
+    uint32_t l[8], r[8];
+    for (int w = 0; w < 8; ++w) {
+      const size_t o = 32 * (size_t)i + 4 * w;
+      const uint32_t s = ((uint32_t)proof[o] << 24) | ((uint32_t)proof[o + 1] << 16) | ((uint32_t)proof[o + 2] << 8) |
+                         (uint32_t)proof[o + 3];
+      l[w] = sib_left ? s : v[w];
+      r[w] = sib_left ? v[w] : s;
+    }
+    sha256_pair(v, l, r);
+  }
 }
 
 }  // namespace bls381

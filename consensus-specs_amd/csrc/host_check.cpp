@@ -299,6 +299,21 @@ int hc_ssz_root(const uint8_t* item, const uint32_t* prog, uint32_t plen, uint8_
   return 1;
 }
 
+// verify_merkle_branch (bls381_ssz.hpp merkle_branch_root, the fold k_merkle_branch runs): 1 / 0
+int hc_merkle_branch(const uint8_t* leaf32, const uint8_t* proof, uint32_t depth, uint64_t index,
+                     const uint8_t* root32) {
+  if (depth > 64) return 0;
+  uint32_t v[8];
+  for (int w = 0; w < 8; ++w)
+    v[w] = ((uint32_t)leaf32[4 * w] << 24) | ((uint32_t)leaf32[4 * w + 1] << 16) | ((uint32_t)leaf32[4 * w + 2] << 8) |
+           (uint32_t)leaf32[4 * w + 3];
+  merkle_branch_root(v, proof, depth, index);
+  uint32_t d = 0;
+  for (int w = 0; w < 8; ++w)
+    for (int b = 0; b < 4; ++b) d |= (uint32_t)((uint8_t)(v[w] >> (24 - 8 * b)) ^ root32[4 * w + b]);
+  return d == 0;
+}
+
 #if defined(BLS_COUNT_OPS)
 // Per-stage MAC counts (BLS_COUNT_MACS: partial products of the Fp products, 392 per
 // fp_mul) of one bls_verify exactly as the gfx950
@@ -503,6 +518,13 @@ uint32_t hc_deposit_prog(uint32_t* out, size_t* item_size) {
   std::memcpy(out, DEPOSIT_SIGNING_PROG, sizeof(DEPOSIT_SIGNING_PROG));
   *item_size = DEPOSIT_DATA_BYTES;
   return DEPOSIT_SIGNING_PROG_LEN;
+}
+
+// the deposit leaf program, hash_tree_root(DepositData); *item_size = the serialized Deposit's bytes
+uint32_t hc_deposit_root_prog(uint32_t* out, size_t* item_size) {
+  std::memcpy(out, DEPOSIT_ROOT_PROG, sizeof(DEPOSIT_ROOT_PROG));
+  *item_size = DEPOSIT_BYTES;
+  return DEPOSIT_ROOT_PROG_LEN;
 }
 
 }  // extern "C"

@@ -346,6 +346,65 @@ size_t bls381_verify_deposits_workspace_size(size_t n);
 int bls381_verify_deposits_device(size_t n, const uint8_t* d_deposit_data, const uint8_t* d_dom8s,
                                   uint8_t* d_verdicts, void* d_workspace, void* stream);
 
+/* ---- Merkle branches and process_deposit over the registry -------------- */
+/* verify_merkle_branch (0_beacon-chain.md:846-857; also the custody game and
+ * light_client/sync_protocol.md) for n items, one lane each:
+ *   ok_out[i] = verify_merkle_branch(leaves32[i], proofs[i*depth .. ), depth, indices[i], root_i)
+ * with 32-byte siblings, proofs packed (depth * 32 bytes per item), bit k of the 64-bit
+ * indices[i] choosing the side of sibling k, and root_i = roots32 + i * root_stride;
+ * root_stride is 0 (one root for all items) or 32.  depth == 0 compares the leaf with the
+ * root (proofs may then be NULL).  depth > 64, another root_stride, or a NULL argument with
+ * n > 0 return BLS381_EARG.  The device form is queued on `stream` (not synchronised) and
+ * needs no workspace; d_indices must be 8-byte aligned. */
+int bls381_merkle_branch_batch(size_t n, const uint8_t* leaves32, const uint8_t* proofs, uint32_t depth,
+                               const uint64_t* indices, const uint8_t* roots32, size_t root_stride,
+                               uint8_t* ok_out);
+int bls381_merkle_branch_batch_device(size_t n, const uint8_t* d_leaves32, const uint8_t* d_proofs, uint32_t depth,
+                                      const uint64_t* d_indices, const uint8_t* d_roots32, size_t root_stride,
+                                      uint8_t* d_ok, void* stream);
+
+/* process_deposit (0_beacon-chain.md:1732-1775) for n serialized Deposits (:457-461:
+ * 32 x 32 B of proof, then the 184 B DepositData), with the semantics of calling it on
+ * deposits 0 .. n-1 in order: state.deposit_index starts at first_index, and the validator
+ * pubkeys are the registry's entries.
+ *   *first_bad_proof  the first i whose branch does not lead from hash_tree_root(deposit.data)
+ *       to deposit_root under index first_index + i (the spec's assert), or -1.  When it is
+ *       >= 0 the registry is left untouched whatever `commit` says, and the call returns 0.
+ *   outcome[i]        BLS381_DEPOSIT_*; never depends on the proofs, always filled.  A deposit
+ *       for a key that is registered -- before the call, or by an earlier deposit of this
+ *       batch whose proof of possession held -- is a TOPUP and its signature is not checked; a
+ *       new key with a valid proof of possession is NEW; with an invalid one, SKIPPED.
+ *   validator_index[i]  the entry that holds the key: for a key NEW in this batch,
+ *       size_before + (number of NEW among deposits < i); -1 for a SKIPPED deposit.
+ * Returns the number of NEW deposits, or an error code.  With commit != 0 (and every proof
+ * good) the NEW keys are appended in deposit order, decoded and entered in the table as by
+ * bls381_registry_add; bls381_registry_size and later lookups, aggregations and grouped
+ * verifies see them when the call returns.  If they do not fit the capacity the call returns
+ * BLS381_EARG and the registry is unchanged.  With commit == 0 nothing changes.  Entries
+ * equal validator indices as long as every earlier addition was unique; this call keeps that.
+ * The subgroup policy of the proof-of-possession check is the calling thread's.
+ * Divergence: membership is by key bytes in the registry's table, which omits undecodable
+ * keys.  A registry that was fed an undecodable key through bls381_registry_add treats a
+ * deposit for it as new, and the deposit is then SKIPPED (its proof of possession cannot
+ * hold); a registry grown only by this call cannot hold such a key.
+ * deposit_root and dom8 are host memory in both forms.  The device form takes device
+ * buffers (d_workspace of bls381_registry_process_deposits_workspace_size(n) bytes) and runs
+ * synchronously -- the host needs the count and the proof flag before the registry's size
+ * moves -- as bls381_verify_batch_randomized_device does. */
+#define BLS381_DEPOSIT_BYTES 1208
+#define BLS381_DEPOSIT_SKIPPED 0 /* new key, proof of possession invalid: the spec's early return */
+#define BLS381_DEPOSIT_NEW 1     /* validator appended (or would be, commit == 0) */
+#define BLS381_DEPOSIT_TOPUP 2   /* key already a validator: balance increase, signature not checked */
+int bls381_registry_process_deposits(bls381_registry* reg, size_t n, const uint8_t* deposits, uint64_t first_index,
+                                     const uint8_t deposit_root[32], const uint8_t dom8[8], int commit,
+                                     uint8_t* outcome, int32_t* validator_index, int64_t* first_bad_proof);
+size_t bls381_registry_process_deposits_workspace_size(size_t n);
+int bls381_registry_process_deposits_device(bls381_registry* reg, size_t n, const uint8_t* d_deposits,
+                                            uint64_t first_index, const uint8_t deposit_root[32],
+                                            const uint8_t dom8[8], int commit, uint8_t* d_outcome,
+                                            int32_t* d_validator_index, int64_t* first_bad_proof, void* d_workspace,
+                                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
