@@ -2,6 +2,7 @@
 
 * lib/libbls381.so            -- the product: hipcc --offload-arch=gfx950, C ABI of include/bls381.h
 * lib/libbls381_hostcheck.so  -- test infrastructure: g++ build of the same arithmetic headers
+* lib/libbls381_devcheck.so   -- test infrastructure: gfx950 probe kernels over the lane-pair / quad / octet headers
 * tools/valu_peak             -- integer-VALU peak microbenchmark (roofline denominator)
 """
 import os
@@ -36,10 +37,20 @@ def _run(cmd):
 def build_hip(force=False, extra=(), out=None):
     """out: another target (a measurement variant, variants/<name>/libbls381.so, built with `extra`
     defines and selected at run time through BLS381_LIB)."""
-    os.makedirs(LIB, exist_ok=True)
     out = out or os.path.join(LIB, "libbls381.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
     deps = [os.path.join(CSRC, f) for f in HIP_SOURCES + HEADERS] + [os.path.join(INC, "bls381.h")]
+    return _hipcc_shared(out, HIP_SOURCES, deps, force, extra)
+
+
+def build_devcheck(force=False):
+    """The device check library (csrc/dev_check.hip): the product's hipcc flags, no extra defines."""
+    deps = [os.path.join(CSRC, f) for f in ["dev_check.hip"] + HEADERS if f != "bls381_kernels.hpp"]
+    return _hipcc_shared(os.path.join(LIB, "libbls381_devcheck.so"), ["dev_check.hip"], deps, force)
+
+
+def _hipcc_shared(out, sources, deps, force=False, extra=()):
+    os.makedirs(LIB, exist_ok=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     if not force and _newer(out, deps):
         return out
     import fcntl
@@ -67,7 +78,7 @@ def build_hip(force=False, extra=(), out=None):
                 shutil.copytree(INC, os.path.join(snap, "include"))
                 scs = os.path.join(snap, "csrc")
                 _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I",
-                      os.path.join(snap, "include"), "-I", scs, *extra, *[os.path.join(scs, f) for f in HIP_SOURCES],
+                      os.path.join(snap, "include"), "-I", scs, *extra, *[os.path.join(scs, f) for f in sources],
                       "-o", tmp])
             os.chmod(tmp, 0o755)
             os.replace(tmp, out)
@@ -124,3 +135,4 @@ if __name__ == "__main__":
     build_hostcheck(force, count_ops=True)
     build_valu_peak(force)
     build_hip(force)
+    build_devcheck(force)

@@ -182,6 +182,10 @@ BLS_FP2_CALL fpv_t fp2p_sqr_call(fpv_t a) {
 }
 
 // ------------------------------------------------------------ Fp2 on a pair --
+// Unless a function says otherwise, every operand below is normalized (limbs < 2^28) and weakly
+// reduced (value < 2q) on both lanes, and so is every result; only fp2_mul also takes the lazy sums
+// of fp2_add_lazy (limbs < 2^29, values < 4q).  tests/test_device_arith.py checks each of them at
+// those bounds through the probes of dev_check.hip.
 __device__ __forceinline__ fp2p_t pr_make(const fp_t& v) { fp2p_t r; r.v = v; return r; }
 
 template <> BLS_INLINE fp2p_t e2_zero<fp2p_t>() { return pr_make(fp_zero()); }

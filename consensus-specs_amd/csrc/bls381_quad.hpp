@@ -17,6 +17,11 @@
 // Cross-half moves are DPP quad_perm (full-rate VALU, no LDS).  Control flow
 // must be uniform within a quad: every half-dependent choice below is a
 // per-lane select, never a branch.
+//
+// Preconditions: every Fp2 / Fp6 / Fp12 operand of the quad and octet forms below is normalized
+// (limbs < 2^28) and weakly reduced (value < 2q) on every lane, and so is every result; a value
+// "on both halves" (or both quads) is bit-identical on them.  tests/test_device_arith.py checks
+// each form at those bounds through the probes of dev_check.hip.
 #pragma once
 #include "bls381_pair.hpp"
 
@@ -300,7 +305,8 @@ __device__ __forceinline__ jac_t<fp2p_t> g2_psi_jac_q(const jac_t<fp2p_t>& p) {
   return r;
 }
 
-// [k] a (affine base) and [k] p (Jacobian base) for a 64-bit k, left to right
+// [k] a (affine base) and [k] p (Jacobian base) for a 64-bit k >= 1, left to right (the ladder
+// starts from the base point, so k = 0 returns it; the callers pass |x|)
 __device__ __noinline__ jac_t<fp2p_t> jac_mul_u64_q(const aff_t<fp2p_t> a, uint64_t k) {
   jac_t<fp2p_t> r = jac_from_aff(a);
   int top = 63;

@@ -110,6 +110,93 @@ void hc_cyc_csqr_raw(const uint8_t* in, uint8_t* out) {
   straw2(out, r.g2); straw2(out + 96, r.g3); straw2(out + 192, r.g4); straw2(out + 288, r.g5);
 }
 
+}  // extern "C"
+namespace {
+// raw limb words (14 x u32 per Fp, Montgomery domain, nothing converted), as hc_fp_lc_raw
+fp_t rw(const uint32_t*& p) { fp_t r; for (int i = 0; i < 14; ++i) r.w[i] = *p++; return r; }
+fp2_t rw2(const uint32_t*& p) { fp2_t r; r.c0 = rw(p); r.c1 = rw(p); return r; }
+fp12_t rw12(const uint32_t*& p) {
+  fp12_t r;
+  r.c0.c0 = rw2(p); r.c0.c1 = rw2(p); r.c0.c2 = rw2(p); r.c1.c0 = rw2(p); r.c1.c1 = rw2(p); r.c1.c2 = rw2(p);
+  return r;
+}
+void ww(uint32_t*& o, const fp_t& a) { for (int i = 0; i < 14; ++i) *o++ = a.w[i]; }
+void ww2(uint32_t*& o, const fp2_t& a) { ww(o, a.c0); ww(o, a.c1); }
+void ww12(uint32_t*& o, const fp12_t& a) {
+  ww2(o, a.c0.c0); ww2(o, a.c0.c1); ww2(o, a.c0.c2); ww2(o, a.c1.c0); ww2(o, a.c1.c1); ww2(o, a.c1.c2);
+}
+jac_t<fp2_t> rwjac(const uint32_t*& p) { jac_t<fp2_t> r; r.x = rw2(p); r.y = rw2(p); r.z = rw2(p); return r; }
+aff_t<fp2_t> rwaff(const uint32_t*& p) { aff_t<fp2_t> r; r.x = rw2(p); r.y = rw2(p); return r; }
+int wwjac(uint32_t*& o, const jac_t<fp2_t>& a) { ww2(o, a.x); ww2(o, a.y); ww2(o, a.z); return jac_is_inf(a) ? 1 : 0; }
+}  // namespace
+extern "C" {
+
+// The one-lane forms on raw limbs, for the operands and expectations of the device check library
+// (dev_check.hip, tests/devcheck_vectors.py): `in` / `out` are sequences of raw Fp in the order of
+// the operation's arguments (Fp2 = c0, c1; Fp12 = a0, a1, a2, b0, b1, b2; points x, y[, z]).
+// Returns the predicate the device probe reports in its flag (infinity, degenerate), else 0.
+int hc_raw_fp2(int op, const uint32_t* in, uint64_t aux, uint32_t* out) {
+  switch (op) {
+    case 0: { const fp2_t a = rw2(in), b = rw2(in); ww2(out, fp2_mul(a, b)); return 0; }   // lazy operands allowed
+    case 1: ww2(out, fp2_sqr(rw2(in))); return 0;
+    case 2: ww2(out, fp2_inv(rw2(in))); return 0;
+    default: {   // cyc_csqr x aux on (g2, g3, g4, g5)
+      cyc_bc<fp2_t> g;
+      g.g2 = rw2(in); g.g3 = rw2(in); g.g4 = rw2(in); g.g5 = rw2(in);
+      for (uint64_t j = 0; j < aux; ++j) g = cyc_csqr(g);
+      ww2(out, g.g2); ww2(out, g.g3); ww2(out, g.g4); ww2(out, g.g5);
+      return 0;
+    }
+  }
+}
+// op 0 mul, 1 sqr, 2 cyclotomic sqr, 3 mul_by_line (f, c0, c1, c2), 4 frob (aux = p), 5 inv, 6 final_exp,
+// 7 cyc_exp_x, 8 cyc_exp_x_gs, 9 cyc_decompress (g2..g5, 1 / (4 g2))
+int hc_raw_fp12(int op, const uint32_t* in, uint64_t aux, uint32_t* out) {
+  const fp12_t f = op == 9 ? fp12_one<fp2_t>() : rw12(in);
+  switch (op) {
+    case 0: ww12(out, fp12_mul(f, rw12(in))); return 0;
+    case 1: ww12(out, fp12_sqr(f)); return 0;
+    case 2: ww12(out, fp12_cyclotomic_sqr(f)); return 0;
+    case 3: { const fp2_t c0 = rw2(in), c1 = rw2(in), c2 = rw2(in); ww12(out, fp12_mul_by_line(f, c0, c1, c2)); return 0; }
+    case 4: ww12(out, fp12_frob(f, (int)aux)); return 0;
+    case 5: ww12(out, fp12_inv(f)); return 0;
+    case 6: ww12(out, final_exp(f)); return 0;
+    case 7: ww12(out, cyc_exp_x<fp2_t, 1>(f)); return 0;
+    case 8: ww12(out, cyc_exp_x_gs(f)); return 0;
+    default: {
+      cyc_bc<fp2_t> g;
+      g.g2 = rw2(in); g.g3 = rw2(in); g.g4 = rw2(in); g.g5 = rw2(in);
+      ww12(out, cyc_decompress(g, rw2(in)));
+      return 0;
+    }
+  }
+}
+// op 0 jac_dbl, 1 jac_add_aff, 2 jac_add, 3 g2_psi_jac, 4 jac_mul_u64 (aux = k >= 1), 5 g2_mul_bp
+int hc_raw_g2(int op, const uint32_t* in, uint64_t aux, uint32_t* out) {
+  switch (op) {
+    case 0: return wwjac(out, jac_dbl(rwjac(in)));
+    case 1: { const jac_t<fp2_t> p = rwjac(in); return wwjac(out, jac_add_aff(p, rwaff(in))); }
+    case 2: { const jac_t<fp2_t> p = rwjac(in); return wwjac(out, jac_add(p, rwjac(in))); }
+    case 3: return wwjac(out, g2_psi_jac(rwjac(in)));
+    case 4: return wwjac(out, jac_mul_u64(rwaff(in), aux));
+    default: return wwjac(out, g2_mul_bp(rwaff(in)));
+  }
+}
+// Miller loop of n <= 2 pairs, each Q (x, y in Fp2) then P (x, y in Fp); returns degenerate
+int hc_raw_miller(int n, const uint32_t* in, uint32_t* out) {
+  aff_t<fp2_t> Q[2];
+  g1_line_pre P[2];
+  if (n < 1 || n > 2) return -1;
+  for (int k = 0; k < n; ++k) {
+    Q[k] = rwaff(in);
+    aff_t<fp_t> p; p.x = rw(in); p.y = rw(in);
+    P[k] = g1_prepare(p);
+  }
+  bool degen = false;
+  ww12(out, n == 1 ? miller_loop_n<1>(Q, P, degen) : miller_loop_n<2>(Q, P, degen));
+  return degen ? 1 : 0;
+}
+
 void hc_fp12_mul(const uint8_t* a, const uint8_t* b, uint8_t* o) { st12(o, fp12_mul(ld12(a), ld12(b))); }
 void hc_fp12_sqr(const uint8_t* a, uint8_t* o) { st12(o, fp12_sqr(ld12(a))); }
 void hc_fp12_inv(const uint8_t* a, uint8_t* o) { st12(o, fp12_inv(ld12(a))); }

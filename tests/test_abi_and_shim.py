@@ -176,16 +176,18 @@ def test_rccl_path_resolves_without_a_device():
     assert os.path.realpath(p) in comm.loaded_rccl_paths()
 
 
-def test_library_has_no_flat_instructions():
+@pytest.mark.parametrize("libname", ["libbls381.so", "libbls381_devcheck.so"])
+def test_library_has_no_flat_instructions(libname):
     """VERDICT r05 weak #6 / DESIGN.md section 10.8: no generic (flat) memory access in the shipped
     gfx950 code object.  Round 5 removed every pointer into a caller's private memory from the
     call boundaries (by-value operands, force-inlined reference helpers, address_space(1) SoA
     accessors): a flat access to the private aperture is the fault class of the round-2 max-ilp
-    and round-5 BLS_FP2_INLINE=2 builds.  Static check of lib/libbls381.so (no GPU)."""
+    and round-5 BLS_FP2_INLINE=2 builds.  Static check of lib/libbls381.so, and of the device check
+    library lib/libbls381_devcheck.so, whose probes follow the same discipline (no GPU)."""
     import subprocess
     import sys
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    so = os.path.join(ROOT, "consensus-specs_amd", "lib", "libbls381.so")
+    so = os.path.join(ROOT, "consensus-specs_amd", "lib", libname)
     if not os.path.exists(objdump) or not os.path.exists(so):
         pytest.skip("llvm-objdump or the built library missing")
     sys.path.insert(0, os.path.join(ROOT, "tools"))

@@ -13,6 +13,7 @@ import pytest
 
 import bls_oracle as O
 import tower_model as M
+from devcheck_vectors import csqr_expect_raw as _csqr_expect
 
 q = O.q
 
@@ -165,19 +166,6 @@ def test_fp2_lazy_operands_at_bounds(L):
         e = M.mul2(a, b)
         assert r0 < 2 * q and r1 < 2 * q
         assert (r0 % q, r1 % q) == (e[0] * Rinv % q, e[1] * Rinv % q)
-
-
-def _csqr_expect(g, Rinv):
-    """Karabina outputs (cyc_csqr) on Montgomery-domain raw values, mod q."""
-    mm = lambda a, b: tuple(x * Rinv % q for x in M.mul2(a, b))
-    xi = lambda a: ((a[0] - a[1]) % q, (a[0] + a[1]) % q)
-    add = lambda *xs: tuple(sum(x[i] for x in xs) % q for i in range(2))
-    sc = lambda k, a: (k * a[0] % q, k * a[1] % q)
-    g2, g3, g4, g5 = g
-    return (add(sc(6, xi(mm(g4, g5))), sc(2, g2)),
-            add(sc(3, add(mm(g4, g4), xi(mm(g5, g5)))), sc(-2, g3)),
-            add(sc(3, add(mm(g2, g2), xi(mm(g3, g3)))), sc(-2, g4)),
-            add(sc(6, mm(g2, g3)), sc(2, g5)))
 
 
 def test_cyc_csqr_lazy_at_bounds(L):
