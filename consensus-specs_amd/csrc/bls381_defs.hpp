@@ -33,6 +33,17 @@
 #define BLS_CONST static constexpr
 #endif
 
+// BLS_KEEP_ORDER(x): x, computed where the source computes it.  The optimizer sorts the terms of a
+// sum by how late their operands become available, so a column's incoming carry -- its latest
+// operand -- would be added last, by a 64-bit add of its own, instead of being the addend of the
+// column's first multiply-add.  The annotation ends the sum the optimizer may reorder; it has no
+// instruction of its own.  Other compilers (the host unit-test build) need nothing.
+#if defined(__clang__)
+#define BLS_KEEP_ORDER(x) __builtin_annotation((x), "bls381.order")
+#else
+#define BLS_KEEP_ORDER(x) (x)
+#endif
+
 namespace bls381 {
 
 // Fp element: 14 limbs of 28 bits held in u32 words, little-endian, Montgomery

@@ -1,8 +1,8 @@
 // BLS12-381 base field Fp and the tower Fp2 / Fp6 / Fp12.
 //
 // Fp: 14 limbs x 28 bits, Montgomery form R = 2^392.  Every 28x28-bit partial
-// product accumulates in place into a 64-bit column (one v_mad_u64_u32, no
-// carry chain); carries are resolved once per reduction row.
+// product accumulates into a 64-bit column (one v_mad_u64_u32, no carry
+// chain); a column's carry is the first addend of the next (fp_mont_columns).
 // Tower (DESIGN.md "Data layout"):  Fp2 = Fp[u]/(u^2+1),
 // Fp6 = Fp2[v]/(v^3 - (1+u)),  Fp12 = Fp6[w]/(w^2 - v)  (w^6 = 1+u).
 // Algorithms are mirrored 1:1 by oracle/tower_model.py (test infrastructure).
@@ -212,66 +212,66 @@ BLS_INLINE fp_t fp_half(const fp_t& a) {
   return r;
 }
 
+// Montgomery reduction fused with the product that feeds it, in column order.
+// col(k, acc) returns acc plus the product terms of column k (k = 0..26).  Column k's
+// accumulator starts as the carry out of column k - 1, takes the column's products and
+// the reduction products m_i q_(k-i) of the rows i < k, and for k < 14 yields its own
+// m_k; so the carry rides on the addend of the column's first MAC and no column costs a
+// separate 64-bit add (the row-order form paid one per row and one per output limb).
+// Column bound: the caller's product terms plus <= 14 reduction products < 2^56 plus a
+// carry < 2^36 must stay below 2^64, which the callers state.  Value < q R in, so the
+// result is normalized with value < 2q (its top limb is the last carry).
+// Every multiply-add of the chain is an fp_mac, which keeps the chain in this order
+// (BLS_KEEP_ORDER, bls381_defs.hpp); a plain sum would have its carry moved to the end.
+// tests/test_leaf_columns.py holds the same order on Python integers.
+BLS_INLINE uint64_t fp_mac(uint64_t acc, uint32_t x, uint32_t y) { return BLS_KEEP_ORDER(acc + (uint64_t)x * y); }
+
+template <class F>
+BLS_INLINE fp_t fp_mont_columns(const F& col) {
+  uint32_t m[14];
+  fp_t r;
+  uint64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    uint64_t acc = col(k, c);
+#pragma unroll
+    for (int i = (k > 13 ? k - 13 : 0); i < k && i < 14; ++i) acc = fp_mac(acc, m[i], Q_LIMBS[k - i]);
+    if (k < 14) {
+      m[k] = ((uint32_t)acc * Q_INV28) & FP_MASK;
+      acc = fp_mac(acc, m[k], Q_LIMBS[0]);
+    } else {
+      r.w[k - 14] = (uint32_t)acc & FP_MASK;
+    }
+    c = acc >> 28;
+  }
+  r.w[13] = (uint32_t)c & FP_MASK;
+  return r;
+}
+
 // Montgomery product a * b * 2^-392 mod q.  Inputs: limbs < 2^30 and
 // value(a) * value(b) < 2900 q^2 (e.g. both < 4q lazily summed).  Output:
 // normalized, value < 2q.  Column k accumulates <= 14 products < 2^60 plus
 // <= 14 reduction products < 2^56 and a carry < 2^36: < 2^64.
 BLS_INLINE fp_t fp_mul_body(const fp_t& a, const fp_t& b) {
-  uint64_t T[28];
+  return fp_mont_columns([&](int k, uint64_t acc) {
 #pragma unroll
-  for (int k = 0; k < 28; ++k) T[k] = 0;
-#pragma unroll
-  for (int i = 0; i < 14; ++i)
-#pragma unroll
-    for (int j = 0; j < 14; ++j) T[i + j] += (uint64_t)a.w[i] * b.w[j];
-#pragma unroll
-  for (int i = 0; i < 14; ++i) {
-    const uint32_t m = ((uint32_t)T[i] * Q_INV28) & FP_MASK;
-#pragma unroll
-    for (int j = 0; j < 14; ++j) T[i + j] += (uint64_t)m * Q_LIMBS[j];
-    T[i + 1] += T[i] >> 28;
-  }
-  fp_t r;
-  uint64_t c = 0;
-#pragma unroll
-  for (int j = 0; j < 14; ++j) {
-    const uint64_t v = T[14 + j] + c;
-    r.w[j] = (uint32_t)v & FP_MASK;
-    c = v >> 28;
-  }
-  return r;
+    for (int i = (k > 13 ? k - 13 : 0); i <= k && i < 14; ++i) acc = fp_mac(acc, a.w[i], b.w[k - i]);
+    return acc;
+  });
 }
 
-// squaring: 105 products instead of 196 (cross products doubled via 2a_i)
+// squaring: 105 products instead of 196 (cross products doubled via 2a_i); the same
+// column sums as fp_mul_body(a, a)
 BLS_INLINE fp_t fp_sqr_body(const fp_t& a) {
-  uint64_t T[28];
   uint32_t a2[14];
 #pragma unroll
-  for (int k = 0; k < 28; ++k) T[k] = 0;
-#pragma unroll
   for (int i = 0; i < 14; ++i) a2[i] = a.w[i] << 1;
+  return fp_mont_columns([&](int k, uint64_t acc) {
 #pragma unroll
-  for (int i = 0; i < 14; ++i) {
-    T[2 * i] += (uint64_t)a.w[i] * a.w[i];
-#pragma unroll
-    for (int j = i + 1; j < 14; ++j) T[i + j] += (uint64_t)a2[i] * a.w[j];
-  }
-#pragma unroll
-  for (int i = 0; i < 14; ++i) {
-    const uint32_t m = ((uint32_t)T[i] * Q_INV28) & FP_MASK;
-#pragma unroll
-    for (int j = 0; j < 14; ++j) T[i + j] += (uint64_t)m * Q_LIMBS[j];
-    T[i + 1] += T[i] >> 28;
-  }
-  fp_t r;
-  uint64_t c = 0;
-#pragma unroll
-  for (int j = 0; j < 14; ++j) {
-    const uint64_t v = T[14 + j] + c;
-    r.w[j] = (uint32_t)v & FP_MASK;
-    c = v >> 28;
-  }
-  return r;
+    for (int i = (k > 13 ? k - 13 : 0); 2 * i < k; ++i) acc = fp_mac(acc, a2[i], a.w[k - i]);
+    if ((k & 1) == 0) acc = fp_mac(acc, a.w[k / 2], a.w[k / 2]);
+    return acc;
+  });
 }
 
 // Call boundary.  clang passes an aggregate argument in registers only while the

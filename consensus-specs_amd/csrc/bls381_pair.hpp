@@ -132,7 +132,9 @@ __device__ __forceinline__ fp_t fp_sel(bool c, const fp_t& a, const fp_t& b) {
 // lane 0: a0 b0 + a1 (8q - b1) = Re(ab);  lane 1: a1 b0 + a0 b1 = Im(ab).
 // Operands may be lazy sums (limbs < 2^29, values < 4q).  Column k holds <= 14
 // products < 2^58 plus <= 14 products < 2^59 and the reduction's 14 products
-// < 2^56: < 2^63.5.  The sum is < 48 q^2 < q R, so the result is < 2q.
+// < 2^56 and the carry of the column before (< 2^36): < 2^63.5.  The sum is < 48 q^2 < q R, so
+// the result is < 2q.  Column order (fp_mont_columns): the carry is the addend of the column's
+// first product.
 __device__ __forceinline__ fp_t fp2p_mul_body(const fp_t& a, const fp_t& b) {
   const bool odd = pr_odd();
   const fp_t ao = pr_dpp<DPP_SWAP>(a);
@@ -141,17 +143,14 @@ __device__ __forceinline__ fp_t fp2p_mul_body(const fp_t& a, const fp_t& b) {
   uint32_t w[14];
 #pragma unroll
   for (int k = 0; k < 14; ++k) w[k] = odd ? b1.w[k] : Q8S_LIMBS[k] - b1.w[k];
-  uint64_t T[28];
+  return fp_mont_columns([&](int k, uint64_t acc) {
 #pragma unroll
-  for (int k = 0; k < 28; ++k) T[k] = 0;
-#pragma unroll
-  for (int i = 0; i < 14; ++i)
-#pragma unroll
-    for (int j = 0; j < 14; ++j) {
-      T[i + j] += (uint64_t)a.w[i] * b0.w[j];
-      T[i + j] += (uint64_t)ao.w[i] * w[j];
+    for (int i = (k > 13 ? k - 13 : 0); i <= k && i < 14; ++i) {
+      acc = fp_mac(acc, a.w[i], b0.w[k - i]);
+      acc = fp_mac(acc, ao.w[i], w[k - i]);
     }
-  return fp_redc_wide(T);
+    return acc;
+  });
 }
 
 // lane 0: (a0 + a1)(a0 + 8q - a1) = a0^2 - a1^2;  lane 1: (a0 + a0) a1 = 2 a0 a1.

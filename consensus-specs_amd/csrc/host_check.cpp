@@ -131,6 +131,13 @@ int wwjac(uint32_t*& o, const jac_t<fp2_t>& a) { ww2(o, a.x); ww2(o, a.y); ww2(o
 }  // namespace
 extern "C" {
 
+// the Montgomery products themselves on raw limbs (lazy operands as fp_mul_body / fp_sqr_body allow):
+// op 0 fp_mul(a, b), 1 fp_sqr(a)
+void hc_raw_fp(int op, const uint32_t* in, uint32_t* out) {
+  const fp_t a = rw(in);
+  ww(out, op == 0 ? fp_mul(a, rw(in)) : fp_sqr(a));
+}
+
 // The one-lane forms on raw limbs, for the operands and expectations of the device check library
 // (dev_check.hip, tests/devcheck_vectors.py): `in` / `out` are sequences of raw Fp in the order of
 // the operation's arguments (Fp2 = c0, c1; Fp12 = a0, a1, a2, b0, b1, b2; points x, y[, z]).
