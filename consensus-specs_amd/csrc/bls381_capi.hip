@@ -351,13 +351,13 @@ int launch_final_exp(hipStream_t s, size_t n, const uint32_t* f, const uint8_t* 
 #define BLS_HASH_WIDE_MAX_N 8192
 #endif
 // with the search offsets known, up to this many messages the cofactor map runs on lane octets or
-// quads (k_hash_g2_o / k_hash_g2_q, its independent products two at a time), above on lane pairs
+// quads (k_hash_g2_lg, its independent products two at a time), above on lane pairs
 #ifndef BLS_HASH_QUAD_MAX_N
 #define BLS_HASH_QUAD_MAX_N 8192
 #endif
 // BLS381_ML_OCTET (default 1): the latency Miller loops run one octet per Miller pair
-// (k_miller_verify_oo, k_miller_tasks<8>: 10 product steps per doubling iteration against 19 on a
-// quad); 0 = one quad per pair (k_miller_verify_o, k_miller_tasks<4>)
+// (k_miller_verify_lg<on_octet>, k_miller_tasks<8>: 10 product steps per doubling iteration against 19
+// on a quad); 0 = one quad per pair (k_miller_verify_lg<on_quad>, k_miller_tasks<4>)
 int ml_octet() {
   static const int v = env_knob("BLS381_ML_OCTET", 1);
   return v;
@@ -372,15 +372,15 @@ int launch_hash_g2(hipStream_t s, size_t n, const uint8_t* msgs, uint32_t mlen, 
   return 0;
 }
 // hash_to_G2 with the search offsets known (koff from k_hash_search, or nullptr): the latency
-// batches.  BLS381_HASH_OCT (default 1): the doublings on octets (k_hash_g2_o), 0 = on quads.
+// batches.  BLS381_HASH_OCT (default 1): the doublings on octets (k_hash_g2_lg<on_octet>), 0 = on quads.
 int launch_hash_koff(hipStream_t s, size_t n, const uint8_t* msgs, uint32_t mlen, const uint8_t* doms, int dom_stride,
                      uint32_t* h_aff, uint8_t* st, const uint32_t* koff, int prio) {
   static const int oct = env_knob("BLS381_HASH_OCT", 1);
   if (n <= BLS_HASH_QUAD_MAX_N && oct)
-    LAUNCH("hash_to_g2_o", s, dim3(grid_for(8 * n)), dim3(KBLOCK), k_hash_g2_o, n, msgs, mlen, doms, dom_stride, h_aff,
+    LAUNCH("hash_to_g2_o", s, dim3(grid_for(8 * n)), dim3(KBLOCK), k_hash_g2_lg<on_octet>, n, msgs, mlen, doms, dom_stride, h_aff,
            st, koff, prio);
   else if (n <= BLS_HASH_QUAD_MAX_N)
-    LAUNCH("hash_to_g2_q", s, dim3(grid_for(4 * n)), dim3(KBLOCK), k_hash_g2_q, n, msgs, mlen, doms, dom_stride, h_aff,
+    LAUNCH("hash_to_g2_q", s, dim3(grid_for(4 * n)), dim3(KBLOCK), k_hash_g2_lg<on_quad>, n, msgs, mlen, doms, dom_stride, h_aff,
            st, koff, prio);
   else
     LAUNCH("hash_to_g2", s, dim3(grid_for(2 * n)), dim3(KBLOCK), k_hash_g2, n, msgs, mlen, doms, dom_stride, h_aff,
@@ -452,11 +452,11 @@ int run_verify_pairings(size_t n, const VerifyWs& w, uint8_t* verdicts, hipStrea
   if (n <= BLS_ML_OCT_MAX_N) {
     // lowest latency: one octet (or quad) per Miller pair; the FE multiplies the two values of each item
     if (ml_octet())
-      LAUNCH("miller_loop_2oo", s, dim3(grid_for(16 * n)), b, k_miller_verify_oo, n, (const uint32_t*)w.sig_aff,
+      LAUNCH("miller_loop_2oo", s, dim3(grid_for(16 * n)), b, k_miller_verify_lg<on_octet>, n, (const uint32_t*)w.sig_aff,
              (const uint8_t*)w.sig_st, (const uint32_t*)w.pk_aff, (const uint8_t*)w.pk_st, (const uint32_t*)w.h_aff,
              w.f, w.f_st);
     else
-      LAUNCH("miller_loop_2o", s, dim3(grid_for(8 * n)), b, k_miller_verify_o, n, (const uint32_t*)w.sig_aff,
+      LAUNCH("miller_loop_2o", s, dim3(grid_for(8 * n)), b, k_miller_verify_lg<on_quad>, n, (const uint32_t*)w.sig_aff,
              (const uint8_t*)w.sig_st, (const uint32_t*)w.pk_aff, (const uint8_t*)w.pk_st, (const uint32_t*)w.h_aff,
              w.f, w.f_st);
     return launch_final_exp(s, n, w.f, w.f_st, verdicts, 2);
@@ -576,13 +576,11 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_quads(si
   bool bad_m, bad_o;
   const bool act_m = status(mine, bad_m), act_o = status(other, bad_o);
   if (bad_m || bad_o) { if (lead) st_out[o] = ST_BAD; return; }   // same on all four lanes
-  fq12_t f;
-  bool degen = false;
+  aff_t<fp2p_t> Q;
+  aff_t<fp_t> P;
   if (act_m || act_o) {
     // an idle half runs a copy of the active half's operands with its lines masked to 1
     const int32_t src = act_m ? mine : other;
-    aff_t<fp2p_t> Q;
-    aff_t<fp_t> P;
     if (src >= 0) {
       Q.x = pr_make(soa_ld(h_aff, 2 * G, 2 * (size_t)src + p, 0));
       Q.y = pr_make(soa_ld(h_aff, 2 * G, 2 * (size_t)src + p, 1));
@@ -593,26 +591,15 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_quads(si
       Q.y = pr_make(soa_ld(sig_aff, 2 * ncalls, 2 * c + p, 1));
       P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
     }
-    f = miller_loop_quad(Q, g1_prepare(P), act_m, degen);
-  } else {
-    f = fq12_one();
   }
-  const size_t lp = 2 * o + p;
-  const int c0 = hi ? 3 : 0;
-  soa_st(f_out, 2 * nslots, lp, c0 + 0, f.h.c0.v);
-  soa_st(f_out, 2 * nslots, lp, c0 + 1, f.h.c1.v);
-  soa_st(f_out, 2 * nslots, lp, c0 + 2, f.h.c2.v);
-  if (lead) st_out[o] = degen ? ST_BAD : ST_OK;
+  miller_quad_store(act_m || act_o, Q, P, act_m, true, lead, f_out, st_out, nslots, o);
 }
 
-// each lane multiplies one chunk [begin, end) of Fp12 values (statuses OR-ed);
-// an empty chunk yields 1 (the empty product of an empty call)
-// The latency form of k_miller_quads: pair task t (entry t of quad_pair) on lane
-// quad t, miller_loop_q1 (every step's products split over the halves).  Writes one
+// The latency form of k_miller_quads: pair task t (entry t of quad_pair) on lane group t
+// (miller_pair_store, bls381_kernels.hpp: every step's products split over the group).  Writes one
 // Fp12 (pair SoA over nt values) and status per task: PAIR_NONE or an infinite
 // operand is f = 1; a bad operand or a degenerate loop is ST_BAD.
-// LPI = 4: one quad per pair task (miller_loop_q1); LPI = 8: one octet per task (miller_loop_o1_run,
-// quad A stores)
+// LPI = 4: one quad per pair task; LPI = 8: one octet per task (quad A stores)
 template <int LPI>
 __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_tasks(size_t nt, const int32_t* __restrict__ tasks,
                                                            size_t G, const uint32_t* __restrict__ h_aff,
@@ -624,51 +611,25 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_tasks(si
                                                            const uint32_t* __restrict__ slot, size_t nslots,
                                                            uint32_t* __restrict__ f_out, uint8_t* __restrict__ st_out) {
   static_assert(LPI == 4 || LPI == 8, "quad or octet tasks");
+  using LG = std::conditional_t<LPI == 8, on_octet, on_quad>;
   size_t t;
   bool live;
   if (!lat_unit<LPI>(nt, t, live)) return;
   const bool lead = (threadIdx.x & (LPI - 1u)) == 0 && live;
-  const int p = pr_odd() ? 1 : 0;
   const int32_t src = tasks[t];
   const size_t o = slot ? slot[t] : t;   // output slot (stride nslots)
   uint8_t sq = ST_INF, sp = ST_INF;
   if (src >= 0) { sq = h_st[src]; sp = agg_st[src]; }
   else if (src != PAIR_NONE) { sq = sig_st[(size_t)(-src - 1)]; sp = ST_OK; }
   if (sq == ST_BAD || sp == ST_BAD) { if (lead) st_out[o] = ST_BAD; return; }
-  fq12_t f;
-  bool degen = false;
-  if (sq == ST_OK && sp == ST_OK) {
-    aff_t<fp2p_t> Q;
-    aff_t<fp_t> P;
-    if (src >= 0) {
-      Q.x = pr_make(soa_ld(h_aff, 2 * G, 2 * (size_t)src + p, 0));
-      Q.y = pr_make(soa_ld(h_aff, 2 * G, 2 * (size_t)src + p, 1));
-      P = soa_ld_g1(agg_aff, G, (size_t)src);
-    } else {
-      const size_t c = (size_t)(-src - 1);
-      Q.x = pr_make(soa_ld(sig_aff, 2 * ncalls, 2 * c + p, 0));
-      Q.y = pr_make(soa_ld(sig_aff, 2 * ncalls, 2 * c + p, 1));
-      P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
-    }
-    if (LPI == 8) {
-      const fq12_ml r = miller_loop_o1_run(Q, g1_prepare(P));
-      f = r.f;
-      degen = r.degenerate;
-    } else {
-      f = miller_loop_q1(Q, g1_prepare(P), degen);
-    }
-  } else {
-    f = fq12_one();
-  }
-  if (!live || (LPI == 8 && oc_b())) return;
-  const size_t lp = 2 * o + p;
-  const int c0 = qd_hi() ? 3 : 0;
-  soa_st(f_out, 2 * nslots, lp, c0 + 0, f.h.c0.v);
-  soa_st(f_out, 2 * nslots, lp, c0 + 1, f.h.c1.v);
-  soa_st(f_out, 2 * nslots, lp, c0 + 2, f.h.c2.v);
-  if (lead) st_out[o] = degen ? ST_BAD : ST_OK;
+  // group src >= 0: (H of the group, its aggregate key); else call ~src = -src - 1: (its signature, -[c] g1)
+  const bool grp = src >= 0;
+  miller_pair_store<LG>(sq == ST_OK && sp == ST_OK, grp ? h_aff : sig_aff, grp ? agg_aff : nullptr, grp ? G : ncalls,
+                        (size_t)(grp ? src : ~src), live, lead, f_out, st_out, nslots, o);
 }
 
+// each lane multiplies one chunk [begin, end) of Fp12 values (statuses OR-ed);
+// an empty chunk yields 1 (the empty product of an empty call)
 __global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_fp12_chunk_product(size_t nchunks, const agg_chunk* __restrict__ chunks,
                                                               const uint32_t* __restrict__ in, size_t n_in,
                                                               const uint8_t* __restrict__ in_st,

@@ -7,6 +7,8 @@
 //   lane-pair items: limb k of Fp2 component c of item i, coefficient p, at
 //                    base[(c*14 + k) * 2n + 2i + p]   (lane index 2i + p)
 #pragma once
+#include <type_traits>
+
 #include "bls381_pair.hpp"
 #include "bls381_quad.hpp"
 #include "bls381_ssz.hpp"
@@ -104,6 +106,24 @@ __device__ __forceinline__ fp12p_t soa_ld12(const uint32_t* p, size_t n, size_t 
 __device__ __forceinline__ void soa_st12(uint32_t* p, size_t n, size_t i, const fp12p_t& f) {
   soa_st2p(p, n, i, 0, f.c0.c0); soa_st2p(p, n, i, 1, f.c0.c1); soa_st2p(p, n, i, 2, f.c0.c2);
   soa_st2p(p, n, i, 3, f.c1.c0); soa_st2p(p, n, i, 4, f.c1.c1); soa_st2p(p, n, i, 5, f.c1.c2);
+}
+// this lane's half of an Fp12 on a quad (bls381_quad.hpp) in the same layout: value v of nv, lo the
+// components 0..2, hi 3..5
+__device__ __forceinline__ fq12_t soa_ldq12(const uint32_t* p, size_t nv, size_t v, bool hi) {
+  const size_t lp = 2 * v + (pr_odd() ? 1 : 0);
+  const int c0 = hi ? 3 : 0;
+  fq12_t f;
+  f.h.c0 = pr_make(soa_ld(p, 2 * nv, lp, c0 + 0));
+  f.h.c1 = pr_make(soa_ld(p, 2 * nv, lp, c0 + 1));
+  f.h.c2 = pr_make(soa_ld(p, 2 * nv, lp, c0 + 2));
+  return f;
+}
+__device__ __forceinline__ void soa_stq12(uint32_t* p, size_t nv, size_t v, bool hi, const fq12_t& f) {
+  const size_t lp = 2 * v + (pr_odd() ? 1 : 0);
+  const int c0 = hi ? 3 : 0;
+  soa_st(p, 2 * nv, lp, c0 + 0, f.h.c0.v);
+  soa_st(p, 2 * nv, lp, c0 + 1, f.h.c1.v);
+  soa_st(p, 2 * nv, lp, c0 + 2, f.h.c2.v);
 }
 template <class F> struct soa_jac;
 template <> struct soa_jac<fp_t> {
@@ -213,44 +233,26 @@ __global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_hash_g2(size_t n, 
   if (fin) soa_st_g2(out, n, i, h);
 }
 
-// k_hash_g2 on lane quads (the latency form for small batches): the candidate on both halves as in
-// the pair kernel, the cofactor map with its independent products split over the halves
-// (g2_mul_bp_q, bls381_quad.hpp); the lo pair stores the point.
-__global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_hash_g2_q(size_t n, const uint8_t* __restrict__ msgs, uint32_t mlen,
-                                                     const uint8_t* __restrict__ doms, int dom_stride,
-                                                     uint32_t* __restrict__ out, uint8_t* __restrict__ st,
-                                                     const uint32_t* __restrict__ koff, int prio) {
+// k_hash_g2 on a lane group (the latency form for small batches): the candidate on every pair of
+// the group as in the pair kernel, the cofactor map with its independent products split over the
+// halves and, on_octet, its doublings over the two quads (g2_mul_bp_lg, bls381_quad.hpp); the lo pair
+// of the storing quad stores the point.
+template <class G>
+__global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_hash_g2_lg(size_t n, const uint8_t* __restrict__ msgs, uint32_t mlen,
+                                                      const uint8_t* __restrict__ doms, int dom_stride,
+                                                      uint32_t* __restrict__ out, uint8_t* __restrict__ st,
+                                                      const uint32_t* __restrict__ koff, int prio) {
   if (prio) __builtin_amdgcn_s_setprio(2);
   size_t i;
   bool live;
-  if (!lat_unit<4>(n, i, live)) return;
+  if (!lat_unit<G::LANES>(n, i, live)) return;
   uint8_t dom[8];
   ld_bytes(dom, doms + (size_t)dom_stride * i, 8);
   aff_t<fp2p_t> c;
   hash_to_g2_candidate(c, msgs + (size_t)mlen * i, mlen, dom, koff ? (int)koff[i] : -1);
   aff_t<fp2p_t> h;
-  const bool fin = jac_to_aff(h, g2_mul_bp_q(c));
-  if (qd_hi() || !live) return;
-  if (st && !pr_odd()) st[i] = fin ? ST_OK : ST_INF;
-  if (fin) soa_st_g2(out, n, i, h);
-}
-
-// k_hash_g2_q with the cofactor map's doublings on lane octets (g2_mul_bp_o); quad A's lo pair stores
-__global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_hash_g2_o(size_t n, const uint8_t* __restrict__ msgs, uint32_t mlen,
-                                                     const uint8_t* __restrict__ doms, int dom_stride,
-                                                     uint32_t* __restrict__ out, uint8_t* __restrict__ st,
-                                                     const uint32_t* __restrict__ koff, int prio) {
-  if (prio) __builtin_amdgcn_s_setprio(2);
-  size_t i;
-  bool live;
-  if (!lat_unit<8>(n, i, live)) return;
-  uint8_t dom[8];
-  ld_bytes(dom, doms + (size_t)dom_stride * i, 8);
-  aff_t<fp2p_t> c;
-  hash_to_g2_candidate(c, msgs + (size_t)mlen * i, mlen, dom, koff ? (int)koff[i] : -1);
-  aff_t<fp2p_t> h;
-  const bool fin = jac_to_aff(h, g2_mul_bp_o(c));
-  if (oc_b() || qd_hi() || !live) return;
+  const bool fin = jac_to_aff(h, g2_mul_bp_lg<G>(c));
+  if (!G::stores() || qd_hi() || !live) return;
   if (st && !pr_odd()) st[i] = fin ? ST_OK : ST_INF;
   if (fin) soa_st_g2(out, n, i, h);
 }
@@ -847,18 +849,27 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_ml_accum_q(size
   if (s == ST_BAD) { if (lead) st_out[i] = ST_BAD; return; }
   // the quad's lanes: lo pair reads L's lane-pair slot li (both halves read slot li)
   const fq12_t f = (s == ML_ST_ONE) ? fq12_one() : ml_accum_q_run(L, cnt, li);
-  const int p = pr_odd() ? 1 : 0;
-  const int c0 = qd_hi() ? 3 : 0;
-  soa_st(f_out, 2 * n, 2 * i + p, c0 + 0, f.h.c0.v);
-  soa_st(f_out, 2 * n, 2 * i + p, c0 + 1, f.h.c1.v);
-  soa_st(f_out, 2 * n, 2 * i + p, c0 + 2, f.h.c2.v);
+  soa_stq12(f_out, n, i, qd_hi(), f);
   if (lead) st_out[i] = ST_OK;
+}
+
+// Two Miller pairs on one quad, one per half (miller_loop_quad; `active`: this half's pair takes part,
+// an idle half holds a copy of the other's operands; `any` false: neither does, f = 1 and Q, P are not
+// read), stored as value o of nv in the lane-pair layout of k_ml_accum (each half writes its three Fp2
+// components), so the final exponentiation is shared.
+__device__ __forceinline__ void miller_quad_store(bool any, const aff_t<fp2p_t>& Q, const aff_t<fp_t>& P, bool active,
+                                                  bool live, bool lead, uint32_t* __restrict__ f_out,
+                                                  uint8_t* __restrict__ st_out, size_t nv, size_t o) {
+  bool degen = false;
+  const fq12_t f = any ? miller_loop_quad(Q, g1_prepare(P), active, degen) : fq12_one();
+  if (!live) return;
+  soa_stq12(f_out, nv, o, qd_hi(), f);
+  if (lead) st_out[o] = degen ? ST_BAD : ST_OK;
 }
 
 // The same verify on a lane quad (bls381_quad.hpp): the lo half runs the pair
 // (sig, -g1), the hi half (H(m), pk), side by side; a single finite pair runs on
-// lo with the hi half idle.  f is stored in the lane-pair layout of k_ml_accum (each
-// half writes its three Fp2 components), so the final exponentiation is shared.
+// lo with the hi half idle.
 __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_q(size_t n, const uint32_t* __restrict__ sig_aff,
                                                            const uint8_t* __restrict__ sig_st,
                                                            const uint32_t* __restrict__ pk_aff,
@@ -874,15 +885,14 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_q
   const uint8_t ss = sig_st[i], ps = pk_st[i];
   if (ss == ST_BAD || ps == ST_BAD) { if (lead) st_out[i] = ST_BAD; return; }
   const bool sig_ok = ss == ST_OK, pk_ok = ps == ST_OK;
-  fq12_t f;
-  bool degen = false;
+  bool active = false;
+  aff_t<fp2p_t> Q;
+  aff_t<fp_t> P;
   if (sig_ok || pk_ok) {
     // lo: the signature pair if finite, else the pubkey pair; hi: the pubkey pair when both are
     // finite, else an idle copy of lo's pair (valid operands, its lines masked to 1)
-    const bool active = hi ? (sig_ok && pk_ok) : true;
+    active = hi ? (sig_ok && pk_ok) : true;
     const bool use_pk = (hi && active) || !sig_ok;
-    aff_t<fp2p_t> Q;
-    aff_t<fp_t> P;
     const uint32_t* qsrc = use_pk ? h_aff : sig_aff;
     Q.x = pr_make(soa_ld(qsrc, 2 * n, lp, 0));
     Q.y = pr_make(soa_ld(qsrc, 2 * n, lp, 1));
@@ -891,67 +901,46 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_q
     } else {
       P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
     }
-    f = miller_loop_quad(Q, g1_prepare(P), active, degen);
-  } else {
-    f = fq12_one();
   }
-  if (!live) return;
-  const int c0 = hi ? 3 : 0;
-  soa_st(f_out, 2 * n, lp, c0 + 0, f.h.c0.v);
-  soa_st(f_out, 2 * n, lp, c0 + 1, f.h.c1.v);
-  soa_st(f_out, 2 * n, lp, c0 + 2, f.h.c2.v);
-  if (lead) st_out[i] = degen ? ST_BAD : ST_OK;
+  miller_quad_store(sig_ok || pk_ok, Q, P, active, live, lead, f_out, st_out, n, i);
 }
 
-// The latency form of the verify Miller stage: one quad per Miller pair (miller_loop_q1).
-// Pair task t = 2i + k of item i runs on lanes 4t..4t+3: k = 0 the pair
-// (sig, -[c]g1), k = 1 (BP(H0), pk).  Each task writes its own Fp12 (pair SoA over
-// 2n values) and status; an inactive pair (infinite operand) writes f = 1.
-// k_final_exp_verdict_q<2> multiplies the two.
-__global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_o(size_t n, const uint32_t* __restrict__ sig_aff,
-                                                           const uint8_t* __restrict__ sig_st,
-                                                           const uint32_t* __restrict__ pk_aff,
-                                                           const uint8_t* __restrict__ pk_st,
-                                                           const uint32_t* __restrict__ h_aff,
-                                                           uint32_t* __restrict__ f_out, uint8_t* __restrict__ st_out) {
-  size_t t;
-  bool live;
-  if (!lat_unit<4>(2 * n, t, live)) return;
-  const size_t i = t >> 1;
-  const bool hpair = (t & 1) != 0;
-  const bool lead = (threadIdx.x & 3u) == 0 && live;
-  const int p = pr_odd() ? 1 : 0;
-  const uint8_t ss = sig_st[i], ps = pk_st[i];
-  if (ss == ST_BAD || ps == ST_BAD) { if (lead) st_out[t] = ST_BAD; return; }
+// One Miller pair on a lane group (miller_loop_lg, bls381_quad.hpp), stored as value o of nv (pair SoA)
+// with its status.  The pair is (entry idx of the cnt G2 points q_aff, entry idx of the G1 points
+// p_aff, or -[c] g1 for p_aff null); an inactive pair (an infinite operand, or none) is f = 1.
+template <class G>
+__device__ __forceinline__ void miller_pair_store(bool active, const uint32_t* __restrict__ q_aff,
+                                                  const uint32_t* __restrict__ p_aff, size_t cnt, size_t idx, bool live,
+                                                  bool lead, uint32_t* __restrict__ f_out,
+                                                  uint8_t* __restrict__ st_out, size_t nv, size_t o) {
   fq12_t f;
   bool degen = false;
-  if (hpair ? ps == ST_OK : ss == ST_OK) {
-    const uint32_t* qsrc = hpair ? h_aff : sig_aff;
+  if (active) {
+    const int p = pr_odd() ? 1 : 0;
     aff_t<fp2p_t> Q;
-    Q.x = pr_make(soa_ld(qsrc, 2 * n, 2 * i + p, 0));
-    Q.y = pr_make(soa_ld(qsrc, 2 * n, 2 * i + p, 1));
+    Q.x = pr_make(soa_ld(q_aff, 2 * cnt, 2 * idx + p, 0));
+    Q.y = pr_make(soa_ld(q_aff, 2 * cnt, 2 * idx + p, 1));
     aff_t<fp_t> P;
-    if (hpair) {
-      P = soa_ld_g1(pk_aff, n, i);
+    if (p_aff) {
+      P = soa_ld_g1(p_aff, cnt, idx);
     } else {
       P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
     }
-    f = miller_loop_q1(Q, g1_prepare(P), degen);
+    f = miller_loop_lg<G>(Q, g1_prepare(P), degen);
   } else {
     f = fq12_one();
   }
-  if (!live) return;
-  const size_t lp = 2 * t + p;
-  const int c0 = qd_hi() ? 3 : 0;
-  soa_st(f_out, 4 * n, lp, c0 + 0, f.h.c0.v);
-  soa_st(f_out, 4 * n, lp, c0 + 1, f.h.c1.v);
-  soa_st(f_out, 4 * n, lp, c0 + 2, f.h.c2.v);
-  if (lead) st_out[t] = degen ? ST_BAD : ST_OK;
+  if (!live || !G::stores()) return;
+  soa_stq12(f_out, nv, o, qd_hi(), f);
+  if (lead) st_out[o] = degen ? ST_BAD : ST_OK;
 }
 
-// k_miller_verify_o with one octet per Miller pair (miller_loop_o1_run, bls381_quad.hpp): pair task
-// t = 2i + k of item i on lanes 8t..8t+7; quad A stores f in the layout k_miller_verify_o writes.
-__global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_oo(size_t n, const uint32_t* __restrict__ sig_aff,
+// The latency form of the verify Miller stage: one lane group per Miller pair.  Pair task
+// t = 2i + k of item i runs on lanes G::LANES t ..: k = 0 the pair (sig, -[c]g1), k = 1 (BP(H0), pk).
+// Each task writes its own Fp12 (pair SoA over 2n values) and status; k_final_exp_verdict_q<2> /
+// _oq<2> multiplies the two.
+template <class G>
+__global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_lg(size_t n, const uint32_t* __restrict__ sig_aff,
                                                             const uint8_t* __restrict__ sig_st,
                                                             const uint32_t* __restrict__ pk_aff,
                                                             const uint8_t* __restrict__ pk_st,
@@ -959,39 +948,14 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_miller_verify_o
                                                             uint32_t* __restrict__ f_out, uint8_t* __restrict__ st_out) {
   size_t t;
   bool live;
-  if (!lat_unit<8>(2 * n, t, live)) return;
+  if (!lat_unit<G::LANES>(2 * n, t, live)) return;
   const size_t i = t >> 1;
   const bool hpair = (t & 1) != 0;
-  const bool lead = (threadIdx.x & 7u) == 0 && live;
-  const int p = pr_odd() ? 1 : 0;
+  const bool lead = (threadIdx.x & (G::LANES - 1u)) == 0 && live;
   const uint8_t ss = sig_st[i], ps = pk_st[i];
   if (ss == ST_BAD || ps == ST_BAD) { if (lead) st_out[t] = ST_BAD; return; }
-  fq12_t f;
-  bool degen = false;
-  if (hpair ? ps == ST_OK : ss == ST_OK) {
-    const uint32_t* qsrc = hpair ? h_aff : sig_aff;
-    aff_t<fp2p_t> Q;
-    Q.x = pr_make(soa_ld(qsrc, 2 * n, 2 * i + p, 0));
-    Q.y = pr_make(soa_ld(qsrc, 2 * n, 2 * i + p, 1));
-    aff_t<fp_t> P;
-    if (hpair) {
-      P = soa_ld_g1(pk_aff, n, i);
-    } else {
-      P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
-    }
-    const fq12_ml r = miller_loop_o1_run(Q, g1_prepare(P));
-    f = r.f;
-    degen = r.degenerate;
-  } else {
-    f = fq12_one();
-  }
-  if (!live || oc_b()) return;
-  const size_t lp = 2 * t + p;
-  const int c0 = qd_hi() ? 3 : 0;
-  soa_st(f_out, 4 * n, lp, c0 + 0, f.h.c0.v);
-  soa_st(f_out, 4 * n, lp, c0 + 1, f.h.c1.v);
-  soa_st(f_out, 4 * n, lp, c0 + 2, f.h.c2.v);
-  if (lead) st_out[t] = degen ? ST_BAD : ST_OK;
+  miller_pair_store<G>(hpair ? ps == ST_OK : ss == ST_OK, hpair ? h_aff : sig_aff, hpair ? pk_aff : nullptr, n, i, live,
+                       lead, f_out, st_out, 2 * n, t);
 }
 
 // The throughput final exponentiation (lane pairs).  It runs cyc_exp_x without its exact
@@ -1022,68 +986,44 @@ __global__ void __launch_bounds__(KBLOCK, BLS_FE_WAVES_PER_EU) k_final_exp_redo(
   if (lead) verdict[i] = (uint8_t)v;
 }
 
-// The same verdict on a lane quad (final_exp_q: each half holds one Fp6 half of
-// f and runs half of every Fp12 step): half the per-item latency, for batches
-// that leave SIMDs idle.  Item i's f is the product of NF values NF i + k of the
-// pair-SoA layout k_final_exp_verdict reads (NF = 2: the two Miller pairs of
-// k_miller_verify_o); any value not ST_OK makes the verdict False.
+// The same verdict on a lane group (final_exp_lg, bls381_quad.hpp: each half holds one Fp6 half of
+// f and runs half of every Fp12 step; on an octet both quads hold f and split the products): a
+// fraction of the per-item latency, for batches that leave SIMDs idle.  Item i's f is the product of
+// NF values NF i + k of the pair-SoA layout k_final_exp_verdict reads (NF = 2: the two Miller pairs of
+// k_miller_verify_lg); any value not ST_OK makes the verdict False.  The group's lead lane writes it.
+template <class G, class CS, int NF>
+__device__ __forceinline__ void final_exp_verdict_lg(size_t n, const uint32_t* __restrict__ f_in,
+                                                     const uint8_t* __restrict__ st, uint8_t* __restrict__ verdict) {
+  size_t i;
+  bool live;
+  if (!lat_unit<G::LANES>(n, i, live)) return;
+  const bool lead = (threadIdx.x & (G::LANES - 1u)) == 0 && live;
+  bool ok = true;
+  for (int k = 0; k < NF; ++k) ok = ok && st[NF * i + k] == ST_OK;
+  if (!ok) { if (lead) verdict[i] = 0; return; }
+  const bool hi = qd_hi();
+  fq12_t f = soa_ldq12(f_in, NF * n, NF * i, hi);
+  for (int k = 1; k < NF; ++k) f = G::mul(f, soa_ldq12(f_in, NF * n, NF * i + k, hi));
+  const bool one = fq12_is_one(final_exp_lg<G, CS>(f));
+  if (lead) verdict[i] = one ? 1 : 0;
+}
+
+// on lane quads (BLS381_FE_OCT=0, and every batch above BLS_FE_OCT_MAX_N values)
 template <int NF>
 __global__ void __launch_bounds__(KBLOCK, BLS_FE_WAVES_PER_EU) k_final_exp_verdict_q(size_t n, const uint32_t* __restrict__ f_in,
                                                                const uint8_t* __restrict__ st,
                                                                uint8_t* __restrict__ verdict) {
-  size_t i;
-  bool live;
-  if (!lat_unit<4>(n, i, live)) return;
-  const bool lead = (threadIdx.x & 3u) == 0 && live;
-  bool ok = true;
-  for (int k = 0; k < NF; ++k) ok = ok && st[NF * i + k] == ST_OK;
-  if (!ok) { if (lead) verdict[i] = 0; return; }
-  const int p = pr_odd() ? 1 : 0;
-  const int c0 = qd_hi() ? 3 : 0;
-  const size_t nv = NF * n;
-  auto load = [&](size_t v) {
-    fq12_t g;
-    g.h.c0 = pr_make(soa_ld(f_in, 2 * nv, 2 * v + p, c0 + 0));
-    g.h.c1 = pr_make(soa_ld(f_in, 2 * nv, 2 * v + p, c0 + 1));
-    g.h.c2 = pr_make(soa_ld(f_in, 2 * nv, 2 * v + p, c0 + 2));
-    return g;
-  };
-  fq12_t f = load(NF * i);
-  for (int k = 1; k < NF; ++k) f = fq12_mul(f, load(NF * i + k));
-  const bool one = fq12_is_one(final_exp_q(f));
-  if (lead) verdict[i] = one ? 1 : 0;
+  final_exp_verdict_lg<on_quad, csqr_on_quad, NF>(n, f_in, st, verdict);
 }
 
-// k_final_exp_verdict_q on an octet with the Fp12 products split four ways (final_exp_oq):
-// both quads hold f; quad A's lead lane writes the verdict
-// SQ = 1: the compressed squarings on the octet too (final_exp_oo, BLS381_FE_OCT=3)
+// on lane octets, the Fp12 products split four ways.  SQ = 0: the compressed squarings on quads
+// (BLS381_FE_OCT=2); SQ = 1: on the octet too (co_sqr, BLS381_FE_OCT=3)
 template <int NF, int SQ = 0>
 __global__ void __launch_bounds__(KBLOCK, BLS_FE_WAVES_PER_EU) k_final_exp_verdict_oq(size_t n, const uint32_t* __restrict__ f_in,
                                                                 const uint8_t* __restrict__ st,
                                                                 uint8_t* __restrict__ verdict) {
-  size_t i;
-  bool live;
-  if (!lat_unit<8>(n, i, live)) return;
-  const bool lead = (threadIdx.x & 7u) == 0 && live;
-  bool ok = true;
-  for (int k = 0; k < NF; ++k) ok = ok && st[NF * i + k] == ST_OK;
-  if (!ok) { if (lead) verdict[i] = 0; return; }
-  const int p = pr_odd() ? 1 : 0;
-  const int c0 = qd_hi() ? 3 : 0;
-  const size_t nv = NF * n;
-  auto load = [&](size_t v) {
-    fq12_t g;
-    g.h.c0 = pr_make(soa_ld(f_in, 2 * nv, 2 * v + p, c0 + 0));
-    g.h.c1 = pr_make(soa_ld(f_in, 2 * nv, 2 * v + p, c0 + 1));
-    g.h.c2 = pr_make(soa_ld(f_in, 2 * nv, 2 * v + p, c0 + 2));
-    return g;
-  };
-  fq12_t f = load(NF * i);
-  for (int k = 1; k < NF; ++k) f = fq12_mul_oct(f, load(NF * i + k));
-  const bool one = fq12_is_one(SQ ? final_exp_oo(f) : final_exp_oq(f));
-  if (lead) verdict[i] = one ? 1 : 0;
+  final_exp_verdict_lg<on_octet, std::conditional_t<SQ != 0, csqr_on_octet, csqr_on_quad>, NF>(n, f_in, st, verdict);
 }
-
 
 // ------------------------------------- randomized batch verification (opt-in) --
 // Small-exponent batch test (SURVEY.md §7 "Verdict semantics under batching"):
@@ -1396,7 +1336,7 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_rb_ml_lines(siz
 }
 
 // the signature-sum slot of every sub-batch: (sum_i [r_i] sig_i, -[c] g1), one lane quad
-// per sub-batch (miller_loop_q1, the latency form: nb is small and this branch runs
+// per sub-batch (miller_loop_lg<on_quad>, the latency form: nb is small and this branch runs
 // beside the per-item work)
 // (slot_per: the item value slots per sub-batch; the sum's slot follows them)
 __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_rb_miller_sig(size_t nb, size_t slot_per,
@@ -1415,12 +1355,9 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_rb_miller_sig(s
     Q.x = pr_make(soa_ld(s_aff, 2 * nb, 2 * b + p, 0));
     Q.y = pr_make(soa_ld(s_aff, 2 * nb, 2 * b + p, 1));
     aff_t<fp_t> ng; ng.x = G1_VGEN_X_M; ng.y = G1_VGEN_NEGY_M;
-    f = miller_loop_q1(Q, g1_prepare(ng), degen);
+    f = miller_loop_lg<on_quad>(Q, g1_prepare(ng), degen);
   }
-  const int c0 = qd_hi() ? 3 : 0;
-  soa_st(f_out, 2 * nslots, 2 * slot + p, c0 + 0, f.h.c0.v);
-  soa_st(f_out, 2 * nslots, 2 * slot + p, c0 + 1, f.h.c1.v);
-  soa_st(f_out, 2 * nslots, 2 * slot + p, c0 + 2, f.h.c2.v);
+  soa_stq12(f_out, nslots, slot, qd_hi(), f);
   if ((threadIdx.x & 3u) == 0) st_out[slot] = (st == ST_BAD || degen) ? ST_BAD : ST_OK;
 }
 

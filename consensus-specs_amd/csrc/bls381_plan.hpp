@@ -48,7 +48,7 @@ struct VerifyWs {
   uint8_t *pk_st, *sig_st, *f_st, *ml_st;
 };
 // bls_verify batches of at most this many items run each Miller pair on its own lane
-// quad (k_miller_verify_o, 8 lanes per item: the lowest latency), up to
+// quad or octet (k_miller_verify_lg, 8 or 16 lanes per item: the lowest latency), up to
 // BLS_ML_QUAD_MAX_N both pairs of an item on one quad (k_miller_verify_q), above that
 // the split loop (k_ml_lines -> k_ml_accum: the least work per item)
 #ifndef BLS_ML_OCT_MAX_N
@@ -183,7 +183,7 @@ struct VmPlan {
   std::vector<int32_t> quad_pair;       // 2 per quad: group >= 0, -(call + 1) = the signature pair, or PAIR_NONE
   std::vector<uint32_t> call_quad_off;  // n_calls + 1 offsets into the quads
   ProductPasses passes;                 // segmented Fp12 products (empty: one quad per call)
-  // latency path (small batches): one quad per Miller pair (k_miller_tasks_q1); the pair
+  // latency path (small batches): one quad or octet per Miller pair (k_miller_tasks); the pair
   // tasks are the quad_pair entries, and these passes multiply them per call
   bool tasks = false;
   ProductPasses task_passes;

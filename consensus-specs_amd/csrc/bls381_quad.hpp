@@ -214,7 +214,7 @@ __device__ __forceinline__ void line_dbl_q1(g2_proj<fp2p_t>& T, const g1_line_pr
 }
 
 // ------------------------------------------- G2 point arithmetic on a quad --
-// The latency form of hash_to_G2's cofactor map (k_hash_g2_q): the running point is held on both
+// The latency form of hash_to_G2's cofactor map (g2_mul_bp_lg<on_quad>): the running point is held on both
 // halves and the independent products of each step run on the two halves at once, as in
 // line_dbl_q1.  Every value is the same on both halves after each step, so the exceptional-case
 // branches of the point formulas stay uniform within the quad.  The same formulas as
@@ -305,40 +305,6 @@ __device__ __forceinline__ jac_t<fp2p_t> g2_psi_jac_q(const jac_t<fp2p_t>& p) {
   return r;
 }
 
-// [k] a (affine base) and [k] p (Jacobian base) for a 64-bit k >= 1, left to right (the ladder
-// starts from the base point, so k = 0 returns it; the callers pass |x|)
-__device__ __noinline__ jac_t<fp2p_t> jac_mul_u64_q(const aff_t<fp2p_t> a, uint64_t k) {
-  jac_t<fp2p_t> r = jac_from_aff(a);
-  int top = 63;
-  while (top > 0 && !((k >> top) & 1)) --top;
-  for (int i = top - 1; i >= 0; --i) {
-    r = jac_dbl_q(r);
-    if ((k >> i) & 1) r = jac_add_aff_q(r, a);
-  }
-  return r;
-}
-__device__ __noinline__ jac_t<fp2p_t> jac_mul_u64_jac_q(const jac_t<fp2p_t> p, uint64_t k) {
-  jac_t<fp2p_t> r = p;
-  int top = 63;
-  while (top > 0 && !((k >> top) & 1)) --top;
-  for (int i = top - 1; i >= 0; --i) {
-    r = jac_dbl_q(r);
-    if ((k >> i) & 1) r = jac_add_q(r, p);
-  }
-  return r;
-}
-
-// g2_mul_bp (bls381_hash.hpp) on a quad: BP(P) = [x^2 - x - 1]P + [x - 1]psi(P) + 2 psi^2(P)
-__device__ __noinline__ jac_t<fp2p_t> g2_mul_bp_q(const aff_t<fp2p_t> p) {
-  aff_t<fp2p_t> np;
-  np.x = p.x;
-  np.y = fp2_neg(p.y);
-  const jac_t<fp2p_t> t1 = jac_mul_u64_q(p, BLS_X_ABS);                                   // [|x|]P
-  jac_t<fp2p_t> Q0 = jac_add_aff_q(jac_add_q(jac_mul_u64_jac_q(t1, BLS_X_ABS), t1), np);  // [x^2 - x - 1]P
-  Q0 = jac_add_q(Q0, g2_psi_jac_q(jac_add_aff_q(jac_neg(t1), np)));                      // + psi([x - 1]P)
-  return jac_add_q(Q0, g2_psi_jac_q(g2_psi_jac_q(jac_dbl_q(jac_from_aff(p)))));          // + psi^2(2P)
-}
-
 // line_add with its products split (lo | hi per step)
 __device__ __forceinline__ void line_add_q1(g2_proj<fp2p_t>& T, const aff_t<fp2p_t>& Q, const g1_line_pre& P,
                                             fp2p_t& c0, fp2p_t& c1, fp2p_t& c2) {
@@ -404,35 +370,6 @@ __device__ __forceinline__ fq12_t fq12_mul_by_line_q1(const fq12_t& f, const fp2
   return r;
 }
 
-// Miller loop of one pair on a quad; returns conj(f) (x < 0).  degenerate as in miller_loop_n.
-__device__ __noinline__ fq12_ml miller_loop_q1_run(const aff_t<fp2p_t> Q, const g1_line_pre P) {
-  g2_proj<fp2p_t> T;
-  T.x = Q.x; T.y = Q.y; T.z = e2_one<fp2p_t>();
-  fq12_t f = fq12_one();
-  bool first = true;
-  for (int i = 62; i >= 0; --i) {
-    fp2p_t c0, c1, c2;
-    line_dbl_q1(T, P, c0, c1, c2);
-    if (!first) f = fq12_sqr(f);
-    f = fq12_mul_by_line_q1(f, c0, c1, c2);
-    first = false;
-    if ((BLS_X_ABS >> i) & 1) {
-      line_add_q1(T, Q, P, c0, c1, c2);
-      f = fq12_mul_by_line_q1(f, c0, c1, c2);
-    }
-  }
-  fq12_ml r;
-  r.degenerate = fp2_is_zero(T.z);   // T is the same on all four lanes
-  r.f = fq12_conj(f);
-  return r;
-}
-
-__device__ __forceinline__ fq12_t miller_loop_q1(const aff_t<fp2p_t>& Q, const g1_line_pre& P, bool& degenerate) {
-  const fq12_ml r = miller_loop_q1_run(Q, P);
-  degenerate = r.degenerate;
-  return r.f;
-}
-
 // ----------------------------------------------- one Miller pair per octet --
 // The lowest-latency Miller loop: one pair on 8 lanes, two quads (A = lanes 8t..8t+3, B = 8t+4..8t+7)
 // that both hold T and f in the quad layout above.  Each step's independent products run on all
@@ -458,7 +395,7 @@ __device__ __forceinline__ void oc_both(const fp2p_t& mine, fp2p_t& a_v, fp2p_t&
   b_v = qd_sel(b, mine, o);
 }
 
-// ----------------------------------------- G2 doubling on an octet (k_hash_g2_o) --
+// --------------------------------- G2 doubling on an octet (g2_mul_bp_lg<on_octet>) --
 // The point on both quads; the doubling's independent products on the octet's four lane pairs
 // (slot = 2 * quad B + hi): X^2 | Y^2 | Y Z, then B^2 | (X + B)^2 | E^2, then E (D - X3) -- 3 product
 // times against jac_dbl_q's 4.  The additions stay in the quad form (both quads compute them).
@@ -492,38 +429,6 @@ __device__ __forceinline__ jac_t<fp2p_t> jac_dbl_o(const jac_t<fp2p_t>& p) {
   r.y = fp2_sub(fp2_mul(E, fp2_sub(D, r.x)), fp2_mul_small(C, 8));
   r.z = fp2_dbl(YZ);
   return r;   // Z = 0 stays 0
-}
-
-__device__ __noinline__ jac_t<fp2p_t> jac_mul_u64_o(const aff_t<fp2p_t> a, uint64_t k) {
-  jac_t<fp2p_t> r = jac_from_aff(a);
-  int top = 63;
-  while (top > 0 && !((k >> top) & 1)) --top;
-  for (int i = top - 1; i >= 0; --i) {
-    r = jac_dbl_o(r);
-    if ((k >> i) & 1) r = jac_add_aff_q(r, a);
-  }
-  return r;
-}
-__device__ __noinline__ jac_t<fp2p_t> jac_mul_u64_jac_o(const jac_t<fp2p_t> p, uint64_t k) {
-  jac_t<fp2p_t> r = p;
-  int top = 63;
-  while (top > 0 && !((k >> top) & 1)) --top;
-  for (int i = top - 1; i >= 0; --i) {
-    r = jac_dbl_o(r);
-    if ((k >> i) & 1) r = jac_add_q(r, p);
-  }
-  return r;
-}
-
-// g2_mul_bp_q with the ladders' doublings on the octet
-__device__ __noinline__ jac_t<fp2p_t> g2_mul_bp_o(const aff_t<fp2p_t> p) {
-  aff_t<fp2p_t> np;
-  np.x = p.x;
-  np.y = fp2_neg(p.y);
-  const jac_t<fp2p_t> t1 = jac_mul_u64_o(p, BLS_X_ABS);                                   // [|x|]P
-  jac_t<fp2p_t> Q0 = jac_add_aff_q(jac_add_q(jac_mul_u64_jac_o(t1, BLS_X_ABS), t1), np);  // [x^2 - x - 1]P
-  Q0 = jac_add_q(Q0, g2_psi_jac_q(jac_add_aff_q(jac_neg(t1), np)));                      // + psi([x - 1]P)
-  return jac_add_q(Q0, g2_psi_jac_q(g2_psi_jac_q(jac_dbl_o(jac_from_aff(p)))));          // + psi^2(2P)
 }
 
 // fp6_mul_inl with its six Karatsuba products split A | B (the same formula, bit-identical)
@@ -616,29 +521,6 @@ __device__ __forceinline__ void line_dbl_oct(g2_proj<fp2p_t>& T, const g1_line_p
   T.x = fp2_half(qd_sel(hi, m2o, m2));
   T.y = fp2_sub(qd_sel(hi, s2o, s2), fp2_mul_small(qd_sel(hi, s2, s2o), 3));
   T.z = fp2_dbl(qd_sel(hi, m2, m2o));
-}
-
-// Miller loop of one pair on an octet; returns conj(f) (x < 0) in the quad form on both quads.
-__device__ __noinline__ fq12_ml miller_loop_o1_run(const aff_t<fp2p_t> Q, const g1_line_pre P) {
-  g2_proj<fp2p_t> T;
-  T.x = Q.x; T.y = Q.y; T.z = e2_one<fp2p_t>();
-  fq12_t f = fq12_one();
-  bool first = true;
-  for (int i = 62; i >= 0; --i) {
-    fp2p_t c0, c1, c2;
-    line_dbl_oct(T, P, c0, c1, c2);
-    if (!first) f = fq12_sqr_oct(f);
-    f = fq12_mul_by_line_oct(f, c0, c1, c2);
-    first = false;
-    if ((BLS_X_ABS >> i) & 1) {
-      line_add_q1(T, Q, P, c0, c1, c2);
-      f = fq12_mul_by_line_oct(f, c0, c1, c2);
-    }
-  }
-  fq12_ml r;
-  r.degenerate = fp2_is_zero(T.z);   // T is the same on all eight lanes
-  r.f = fq12_conj(f);
-  return r;
 }
 
 // ------------------------------------------- final exponentiation on quads --
@@ -767,65 +649,10 @@ __device__ __forceinline__ fq12_t cq_decompress(const cq_t& g, const fp2p_t& inv
   return f;
 }
 
-// exact fallback (cyc_exp_x_gs): generic squarings, valid for every element
-__device__ __noinline__ fq12_t cyc_exp_x_gs_q(const fq12_t f) {
-  fq12_t r = f;
-  for (int s = 0; s < 6; ++s) {
-    for (int j = CYC_X_RUNS[s]; j > 0; --j) r = fq12_sqr(r);
-    if (s < 5) r = fq12_mul(r, f);
-  }
-  return fq12_conj(r);
-}
 
-// f^x (cyc_exp_x): compressed squarings, six snapshots, one shared inversion
-__device__ __noinline__ fq12_t cyc_exp_x_q(const fq12_t f) {
-  const bool hi = qd_hi();
-  cq_t snap[6];
-  cq_t g = cq_compress(f);
-  bool zero = false;
-  for (int s = 0; s < 6; ++s) {
-    for (int j = CYC_X_RUNS_RTL[s]; j > 0; --j) g = cq_sqr(g);
-    snap[s] = g;
-    zero = zero | fp2_is_zero(cq_g2(g));
-  }
-  if (BLS_ANY(zero)) return cyc_exp_x_gs_q(f);
-  fp2p_t pre[6];
-  pre[0] = fp2_mul_small(cq_g2(snap[0]), 4);
-  for (int s = 1; s < 6; ++s) pre[s] = fp2_mul(pre[s - 1], fp2_mul_small(cq_g2(snap[s]), 4));
-  fp2p_t inv = fp2_inv(pre[5]);
-  fq12_t r;
-  for (int s = 5; s >= 0; --s) {
-    fp2p_t is = inv;
-    if (s) {
-      // lo: inv * pre[s-1] (this snapshot's 1/(4 g2)), hi: inv * 4 g2 (the next inv)
-      const fp2p_t p = fp2_mul(inv, qd_sel(hi, fp2_mul_small(cq_g2(snap[s]), 4), pre[s - 1]));
-      const fp2p_t po = qd_swap(p);
-      is = qd_sel(hi, po, p);
-      inv = qd_sel(hi, p, po);
-    }
-    const fq12_t x = cq_decompress(snap[s], is);
-    r = (s == 5) ? x : fq12_mul(r, x);
-  }
-  return fq12_conj(r);
-}
-
-// f^(3 (q^12 - 1)/r), the chain of final_exp
-__device__ inline fq12_t final_exp_q(const fq12_t f) {
-  fq12_t t = fq12_mul(fq12_conj(f), fq12_inv(f));          // f^(q^6 - 1)
-  t = fq12_mul(fq12_frob(t, 2), t);                        // ^(q^2 + 1)
-  fq12_t a = fq12_mul(cyc_exp_x_q(t), fq12_conj(t));       // t^(x-1)
-  a = fq12_mul(cyc_exp_x_q(a), fq12_conj(a));              // t^((x-1)^2)
-  const fq12_t b = fq12_mul(cyc_exp_x_q(a), fq12_frob(a, 1));          // a^(x+q)
-  const fq12_t bx2 = cyc_exp_x_q(cyc_exp_x_q(b));
-  const fq12_t c = fq12_mul(fq12_mul(bx2, fq12_frob(b, 2)), fq12_conj(b));   // b^(x^2+q^2-1)
-  const fq12_t t3 = fq12_mul(fq12_sqr(t), t);
-  return fq12_mul(c, t3);
-}
-
-
-// ---- the final exponentiation on an octet, products split (k_final_exp_verdict_oq) ----
-// The compressed squarings stay in the quad form on both quads (BLS381_FE_OCT=2; the default
-// splits them four ways as well, cyc_exp_x_oo below); every Fp12 product runs its Fp6
+// ---- the Fp12 product of the final exponentiation on an octet (k_final_exp_verdict_oq) ----
+// The compressed squarings stay in the quad form on both quads (csqr_on_quad, BLS381_FE_OCT=2)
+// or are split four ways as well (csqr_on_octet below, the default); every Fp12 product runs its Fp6
 // products over the four lane pairs: fq12_mul 9 product steps -> 5.
 // fp6_mul_split with its three products per half split A: 0, 2 | B: 1, 2 (the same values)
 __device__ __forceinline__ fp6p_t fp6_mul_split_oct(const fp6p_t& s, const fp6p_t& t) {
@@ -858,59 +685,8 @@ __device__ __forceinline__ fq12_t fq12_mul_oct(const fq12_t& f, const fq12_t& g)
   return r;
 }
 
-__device__ __noinline__ fq12_t cyc_exp_x_gs_oq(const fq12_t f) {
-  fq12_t r = f;
-  for (int s = 0; s < 6; ++s) {
-    for (int j = CYC_X_RUNS[s]; j > 0; --j) r = fq12_sqr_oct(r);
-    if (s < 5) r = fq12_mul_oct(r, f);
-  }
-  return fq12_conj(r);
-}
-
-__device__ __noinline__ fq12_t cyc_exp_x_oq(const fq12_t f) {
-  const bool hi = qd_hi();
-  cq_t snap[6];
-  cq_t g = cq_compress(f);
-  bool zero = false;
-  for (int s = 0; s < 6; ++s) {
-    for (int j = CYC_X_RUNS_RTL[s]; j > 0; --j) g = cq_sqr(g);
-    snap[s] = g;
-    zero = zero | fp2_is_zero(cq_g2(g));
-  }
-  if (BLS_ANY(zero)) return cyc_exp_x_gs_oq(f);
-  fp2p_t pre[6];
-  pre[0] = fp2_mul_small(cq_g2(snap[0]), 4);
-  for (int s = 1; s < 6; ++s) pre[s] = fp2_mul(pre[s - 1], fp2_mul_small(cq_g2(snap[s]), 4));
-  fp2p_t inv = fp2_inv(pre[5]);
-  fq12_t r;
-  for (int s = 5; s >= 0; --s) {
-    fp2p_t is = inv;
-    if (s) {
-      const fp2p_t p = fp2_mul(inv, qd_sel(hi, fp2_mul_small(cq_g2(snap[s]), 4), pre[s - 1]));
-      const fp2p_t po = qd_swap(p);
-      is = qd_sel(hi, po, p);
-      inv = qd_sel(hi, p, po);
-    }
-    const fq12_t x = cq_decompress(snap[s], is);
-    r = (s == 5) ? x : fq12_mul_oct(r, x);
-  }
-  return fq12_conj(r);
-}
-
-__device__ inline fq12_t final_exp_oq(const fq12_t f) {
-  fq12_t t = fq12_mul_oct(fq12_conj(f), fq12_inv(f));
-  t = fq12_mul_oct(fq12_frob(t, 2), t);
-  fq12_t a = fq12_mul_oct(cyc_exp_x_oq(t), fq12_conj(t));
-  a = fq12_mul_oct(cyc_exp_x_oq(a), fq12_conj(a));
-  const fq12_t b = fq12_mul_oct(cyc_exp_x_oq(a), fq12_frob(a, 1));
-  const fq12_t bx2 = cyc_exp_x_oq(cyc_exp_x_oq(b));
-  const fq12_t c = fq12_mul_oct(fq12_mul_oct(bx2, fq12_frob(b, 2)), fq12_conj(b));
-  const fq12_t t3 = fq12_mul_oct(fq12_sqr_oct(t), t);
-  return fq12_mul_oct(c, t3);
-}
-
 // ------------------------------------- compressed squarings on a lane octet --
-// The lowest-latency form of cyc_exp_x for single calls: an item's FE runs on 8 lanes,
+// The lowest-latency form of cyc_exp_x's squarings for single calls: an item's FE runs on 8 lanes,
 // two quads holding the same fq12_t (every Fp12 step is computed on both, identically),
 // and only the 63 Karabina squarings per x-power -- most of the FE -- are split four ways:
 // each lane pair of the octet holds one of (g4, g2, g5, g3) (pairs 0..3) and computes that
@@ -991,18 +767,146 @@ __device__ __forceinline__ fp2p_t co_sqr(const fp2p_t& g) {
   return pr_make(fp_6p2_3m2(!sq, R, R, g.v));
 }
 
-// cyc_exp_x_oq with the squarings on the octet as well (co_sqr) -- the single-call FE (BLS381_FE_OCT=3)
-__device__ __noinline__ fq12_t cyc_exp_x_oo(const fq12_t f) {
+// ------------------------------------------------ the lane-group policies --
+// The latency forms below are written once over the group of lanes that holds an item: a quad, or an
+// octet whose two quads hold the same values and split each step's independent products.  A policy
+// only names the primitives above (the five additions of a Miller loop, the point additions and the
+// Frobenius / inverse / decompress steps are the quad forms on either group).
+struct on_quad {
+  static constexpr int LANES = 4;
+  static __device__ __forceinline__ fq12_t mul(const fq12_t& f, const fq12_t& g) { return fq12_mul(f, g); }
+  static __device__ __forceinline__ fq12_t sqr(const fq12_t& f) { return fq12_sqr(f); }
+  static __device__ __forceinline__ fq12_t mul_by_line(const fq12_t& f, const fp2p_t& c0, const fp2p_t& c1,
+                                                       const fp2p_t& c2) {
+    return fq12_mul_by_line_q1(f, c0, c1, c2);
+  }
+  static __device__ __forceinline__ void line_dbl(g2_proj<fp2p_t>& T, const g1_line_pre& P, fp2p_t& c0, fp2p_t& c1,
+                                                  fp2p_t& c2) {
+    line_dbl_q1(T, P, c0, c1, c2);
+  }
+  static __device__ __forceinline__ jac_t<fp2p_t> jac_dbl(const jac_t<fp2p_t>& p) { return jac_dbl_q(p); }
+  // the lanes of the group that write its results
+  static __device__ __forceinline__ bool stores() { return true; }
+};
+struct on_octet {
+  static constexpr int LANES = 8;
+  static __device__ __forceinline__ fq12_t mul(const fq12_t& f, const fq12_t& g) { return fq12_mul_oct(f, g); }
+  static __device__ __forceinline__ fq12_t sqr(const fq12_t& f) { return fq12_sqr_oct(f); }
+  static __device__ __forceinline__ fq12_t mul_by_line(const fq12_t& f, const fp2p_t& c0, const fp2p_t& c1,
+                                                       const fp2p_t& c2) {
+    return fq12_mul_by_line_oct(f, c0, c1, c2);
+  }
+  static __device__ __forceinline__ void line_dbl(g2_proj<fp2p_t>& T, const g1_line_pre& P, fp2p_t& c0, fp2p_t& c1,
+                                                  fp2p_t& c2) {
+    line_dbl_oct(T, P, c0, c1, c2);
+  }
+  static __device__ __forceinline__ jac_t<fp2p_t> jac_dbl(const jac_t<fp2p_t>& p) { return jac_dbl_o(p); }
+  static __device__ __forceinline__ bool stores() { return !oc_b(); }   // quad A
+};
+// How cyc_exp_x carries a run of compressed squarings between two snapshots: the quad's cq_t through
+// cq_sqr (on either group: BLS381_FE_OCT=0 and 2), or one coefficient per lane pair of an octet through
+// co_sqr (BLS381_FE_OCT=3, the single-call FE).
+struct csqr_on_quad {
+  static __device__ __forceinline__ cq_t enter(const cq_t& g) { return g; }
+  static __device__ __forceinline__ cq_t sqr(const cq_t& g) { return cq_sqr(g); }
+  static __device__ __forceinline__ cq_t exit(const cq_t& g) { return g; }
+};
+struct csqr_on_octet {
+  static __device__ __forceinline__ fp2p_t enter(const cq_t& g) { return co_enter(g); }
+  static __device__ __forceinline__ fp2p_t sqr(const fp2p_t& g) { return co_sqr(g); }
+  static __device__ __forceinline__ cq_t exit(const fp2p_t& g) { return co_exit(g); }
+};
+
+// Miller loop of one pair on a lane group; returns conj(f) (x < 0), in the quad form on every quad of
+// the group.  degenerate as in miller_loop_n.
+template <class G>
+__device__ __noinline__ fq12_ml miller_loop_lg_run(const aff_t<fp2p_t> Q, const g1_line_pre P) {
+  g2_proj<fp2p_t> T;
+  T.x = Q.x; T.y = Q.y; T.z = e2_one<fp2p_t>();
+  fq12_t f = fq12_one();
+  bool first = true;
+  for (int i = 62; i >= 0; --i) {
+    fp2p_t c0, c1, c2;
+    G::line_dbl(T, P, c0, c1, c2);
+    if (!first) f = G::sqr(f);
+    f = G::mul_by_line(f, c0, c1, c2);
+    first = false;
+    if ((BLS_X_ABS >> i) & 1) {
+      line_add_q1(T, Q, P, c0, c1, c2);
+      f = G::mul_by_line(f, c0, c1, c2);
+    }
+  }
+  fq12_ml r;
+  r.degenerate = fp2_is_zero(T.z);   // T is the same on all lanes of the group
+  r.f = fq12_conj(f);
+  return r;
+}
+
+template <class G>
+__device__ __forceinline__ fq12_t miller_loop_lg(const aff_t<fp2p_t>& Q, const g1_line_pre& P, bool& degenerate) {
+  const fq12_ml r = miller_loop_lg_run<G>(Q, P);
+  degenerate = r.degenerate;
+  return r.f;
+}
+
+// [k] b for a 64-bit k >= 1 and an affine or a Jacobian base b, left to right (the ladder starts from
+// the base point, so k = 0 returns it; the callers pass |x|)
+__device__ __forceinline__ jac_t<fp2p_t> jac_base(const aff_t<fp2p_t>& b) { return jac_from_aff(b); }
+__device__ __forceinline__ jac_t<fp2p_t> jac_base(const jac_t<fp2p_t>& b) { return b; }
+__device__ __forceinline__ jac_t<fp2p_t> jac_add_base(const jac_t<fp2p_t>& r, const aff_t<fp2p_t>& b) {
+  return jac_add_aff_q(r, b);
+}
+__device__ __forceinline__ jac_t<fp2p_t> jac_add_base(const jac_t<fp2p_t>& r, const jac_t<fp2p_t>& b) {
+  return jac_add_q(r, b);
+}
+template <class G, class B>
+__device__ __noinline__ jac_t<fp2p_t> jac_mul_u64_lg(const B b, uint64_t k) {
+  jac_t<fp2p_t> r = jac_base(b);
+  int top = 63;
+  while (top > 0 && !((k >> top) & 1)) --top;
+  for (int i = top - 1; i >= 0; --i) {
+    r = G::jac_dbl(r);
+    if ((k >> i) & 1) r = jac_add_base(r, b);
+  }
+  return r;
+}
+
+// g2_mul_bp (bls381_hash.hpp) on a lane group: BP(P) = [x^2 - x - 1]P + [x - 1]psi(P) + 2 psi^2(P)
+template <class G>
+__device__ __noinline__ jac_t<fp2p_t> g2_mul_bp_lg(const aff_t<fp2p_t> p) {
+  aff_t<fp2p_t> np;
+  np.x = p.x;
+  np.y = fp2_neg(p.y);
+  const jac_t<fp2p_t> t1 = jac_mul_u64_lg<G>(p, BLS_X_ABS);                                // [|x|]P
+  jac_t<fp2p_t> Q0 = jac_add_aff_q(jac_add_q(jac_mul_u64_lg<G>(t1, BLS_X_ABS), t1), np);   // [x^2 - x - 1]P
+  Q0 = jac_add_q(Q0, g2_psi_jac_q(jac_add_aff_q(jac_neg(t1), np)));                        // + psi([x - 1]P)
+  return jac_add_q(Q0, g2_psi_jac_q(g2_psi_jac_q(G::jac_dbl(jac_from_aff(p)))));           // + psi^2(2P)
+}
+
+// exact fallback (cyc_exp_x_gs): generic squarings, valid for every element
+template <class G>
+__device__ __noinline__ fq12_t cyc_exp_x_gs_lg(const fq12_t f) {
+  fq12_t r = f;
+  for (int s = 0; s < 6; ++s) {
+    for (int j = CYC_X_RUNS[s]; j > 0; --j) r = G::sqr(r);
+    if (s < 5) r = G::mul(r, f);
+  }
+  return fq12_conj(r);
+}
+
+// f^x (cyc_exp_x): compressed squarings carried by CS, six snapshots, one shared inversion
+template <class G, class CS>
+__device__ __noinline__ fq12_t cyc_exp_x_lg(const fq12_t f) {
   const bool hi = qd_hi();
   cq_t snap[6];
-  fp2p_t g = co_enter(cq_compress(f));
+  auto g = CS::enter(cq_compress(f));
   bool zero = false;
   for (int s = 0; s < 6; ++s) {
-    for (int j = CYC_X_RUNS_RTL[s]; j > 0; --j) g = co_sqr(g);
-    snap[s] = co_exit(g);
+    for (int j = CYC_X_RUNS_RTL[s]; j > 0; --j) g = CS::sqr(g);
+    snap[s] = CS::exit(g);
     zero = zero | fp2_is_zero(cq_g2(snap[s]));
   }
-  if (BLS_ANY(zero)) return cyc_exp_x_gs_oq(f);
+  if (BLS_ANY(zero)) return cyc_exp_x_gs_lg<G>(f);
   fp2p_t pre[6];
   pre[0] = fp2_mul_small(cq_g2(snap[0]), 4);
   for (int s = 1; s < 6; ++s) pre[s] = fp2_mul(pre[s - 1], fp2_mul_small(cq_g2(snap[s]), 4));
@@ -1011,27 +915,30 @@ __device__ __noinline__ fq12_t cyc_exp_x_oo(const fq12_t f) {
   for (int s = 5; s >= 0; --s) {
     fp2p_t is = inv;
     if (s) {
+      // lo: inv * pre[s-1] (this snapshot's 1/(4 g2)), hi: inv * 4 g2 (the next inv)
       const fp2p_t p = fp2_mul(inv, qd_sel(hi, fp2_mul_small(cq_g2(snap[s]), 4), pre[s - 1]));
       const fp2p_t po = qd_swap(p);
       is = qd_sel(hi, po, p);
       inv = qd_sel(hi, p, po);
     }
     const fq12_t x = cq_decompress(snap[s], is);
-    r = (s == 5) ? x : fq12_mul_oct(r, x);
+    r = (s == 5) ? x : G::mul(r, x);
   }
   return fq12_conj(r);
 }
 
-__device__ inline fq12_t final_exp_oo(const fq12_t f) {
-  fq12_t t = fq12_mul_oct(fq12_conj(f), fq12_inv(f));
-  t = fq12_mul_oct(fq12_frob(t, 2), t);
-  fq12_t a = fq12_mul_oct(cyc_exp_x_oo(t), fq12_conj(t));
-  a = fq12_mul_oct(cyc_exp_x_oo(a), fq12_conj(a));
-  const fq12_t b = fq12_mul_oct(cyc_exp_x_oo(a), fq12_frob(a, 1));
-  const fq12_t bx2 = cyc_exp_x_oo(cyc_exp_x_oo(b));
-  const fq12_t c = fq12_mul_oct(fq12_mul_oct(bx2, fq12_frob(b, 2)), fq12_conj(b));
-  const fq12_t t3 = fq12_mul_oct(fq12_sqr_oct(t), t);
-  return fq12_mul_oct(c, t3);
+// f^(3 (q^12 - 1)/r), the chain of final_exp
+template <class G, class CS>
+__device__ inline fq12_t final_exp_lg(const fq12_t f) {
+  fq12_t t = G::mul(fq12_conj(f), fq12_inv(f));                    // f^(q^6 - 1)
+  t = G::mul(fq12_frob(t, 2), t);                                  // ^(q^2 + 1)
+  fq12_t a = G::mul(cyc_exp_x_lg<G, CS>(t), fq12_conj(t));            // t^(x-1)
+  a = G::mul(cyc_exp_x_lg<G, CS>(a), fq12_conj(a));                   // t^((x-1)^2)
+  const fq12_t b = G::mul(cyc_exp_x_lg<G, CS>(a), fq12_frob(a, 1));   // a^(x+q)
+  const fq12_t bx2 = cyc_exp_x_lg<G, CS>(cyc_exp_x_lg<G, CS>(b));
+  const fq12_t c = G::mul(G::mul(bx2, fq12_frob(b, 2)), fq12_conj(b));   // b^(x^2+q^2-1)
+  const fq12_t t3 = G::mul(G::sqr(t), t);
+  return G::mul(c, t3);
 }
 
 }  // namespace bls381

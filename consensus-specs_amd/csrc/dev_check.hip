@@ -33,13 +33,17 @@
 //               c * t3, flag = the verdict 0 / 1 / 2)
 //   quad        Q_MUL, Q_SQR, Q_TWO_LINES, Q_MUL_BY_LINE (fq12_mul_by_line_q1), Q_FROB, Q_INV,
 //               Q_CONJ (flag: fq12_is_one), Q_CSQR (cq_compress, cq_sqr x aux, flag: a g2 = 0 seen),
-//               Q_DECOMPRESS (cq_decompress with a given inverse), Q_CYC_EXP_X (cyc_exp_x_q and
-//               cyc_exp_x_gs_q, flag: a snapshot had g2 = 0, the fallback's condition), Q_FINAL_EXP
+//               Q_DECOMPRESS (cq_decompress with a given inverse), Q_CYC_EXP_X (cyc_exp_x_lg and
+//               cyc_exp_x_gs_lg on the quad, flag: a snapshot had g2 = 0, the fallback's condition),
+//               Q_FINAL_EXP (final_exp_lg<on_quad, csqr_on_quad>)
 //   octet       O_MUL, O_SQR, O_MUL_BY_LINE, O_CSQR (cq_compress, co_enter, co_sqr x aux, co_exit),
-//               O_CYC_EXP_X (cyc_exp_x_oq, cyc_exp_x_oo, cyc_exp_x_gs_oq), O_FINAL_EXP_OQ, O_FINAL_EXP_OO
-//   G2          G_DBL_Q, G_ADD_AFF_Q, G_ADD_Q, G_PSI_Q, G_MUL_U64_Q (aux: k), G_MUL_BP_Q, G_DBL_O,
-//               G_MUL_U64_O, G_MUL_BP_O (flag: the result is the point at infinity)
-//   Miller      M_QUAD (aux: bit 0 lo active, bit 1 hi active), M_Q1, M_O1 (flag: degenerate)
+//               O_CYC_EXP_X (cyc_exp_x_lg<on_octet, ..> with csqr_on_quad, then csqr_on_octet, and
+//               cyc_exp_x_gs_lg<on_octet>), O_FINAL_EXP_OQ / _OO (final_exp_lg<on_octet, ..> likewise)
+//   G2          G_DBL_Q, G_ADD_AFF_Q, G_ADD_Q, G_PSI_Q, G_MUL_U64_Q (jac_mul_u64_lg<on_quad>, aux: k),
+//               G_MUL_BP_Q (g2_mul_bp_lg<on_quad>), G_DBL_O, G_MUL_U64_O, G_MUL_BP_O (the same on
+//               on_octet; flag: the result is the point at infinity)
+//   Miller      M_QUAD (aux: bit 0 lo active, bit 1 hi active), M_Q1, M_O1 (miller_loop_lg on the
+//               quad, on the octet; flag: degenerate)
 #include <cstring>
 #include <vector>
 
@@ -163,7 +167,7 @@ __device__ __forceinline__ g1_line_pre mkg1(const fp_t* I) {
   aff_t<fp_t> P; P.x = I[0]; P.y = I[1];
   return g1_prepare(P);
 }
-// the snapshots' g2 = 0 test of cyc_exp_x_q / _oq / _oo (the condition of their exact fallback)
+// the snapshots' g2 = 0 test of cyc_exp_x_lg (the condition of its exact fallback)
 __device__ __forceinline__ bool snapshot_g2_zero(const fq12_t& f) {
   cq_t g = cq_compress(f);
   bool zero = false;
@@ -236,10 +240,10 @@ __device__ __forceinline__ void probe(const fp_t* I, uint64_t aux, fp_t* O, uint
     g.x = pr_make(I[0]); g.y = pr_make(I[1]);
     putq(O, cq_decompress(g, pr_make(I[2])));
   } else if constexpr (OP == Q_CYC_EXP_X) {
-    putq(O, cyc_exp_x_q(mkq(I)));
-    putq(O + 3, cyc_exp_x_gs_q(mkq(I)));
+    putq(O, cyc_exp_x_lg<on_quad, csqr_on_quad>(mkq(I)));
+    putq(O + 3, cyc_exp_x_gs_lg<on_quad>(mkq(I)));
     fl = snapshot_g2_zero(mkq(I)) ? 1u : 0u;
-  } else if constexpr (OP == Q_FINAL_EXP) putq(O, final_exp_q(mkq(I)));
+  } else if constexpr (OP == Q_FINAL_EXP) putq(O, final_exp_lg<on_quad, csqr_on_quad>(mkq(I)));
   else if constexpr (OP == O_MUL) putq(O, fq12_mul_oct(mkq(I), mkq(I + 3)));
   else if constexpr (OP == O_SQR) putq(O, fq12_sqr_oct(mkq(I)));
   else if constexpr (OP == O_MUL_BY_LINE)
@@ -251,21 +255,21 @@ __device__ __forceinline__ void probe(const fp_t* I, uint64_t aux, fp_t* O, uint
     O[0] = r.x.v; O[1] = r.y.v;
     fl = fp2_is_zero(cq_g2(r)) ? 1u : 0u;
   } else if constexpr (OP == O_CYC_EXP_X) {
-    putq(O, cyc_exp_x_oq(mkq(I)));
-    putq(O + 3, cyc_exp_x_oo(mkq(I)));
-    putq(O + 6, cyc_exp_x_gs_oq(mkq(I)));
+    putq(O, cyc_exp_x_lg<on_octet, csqr_on_quad>(mkq(I)));
+    putq(O + 3, cyc_exp_x_lg<on_octet, csqr_on_octet>(mkq(I)));
+    putq(O + 6, cyc_exp_x_gs_lg<on_octet>(mkq(I)));
     fl = snapshot_g2_zero(mkq(I)) ? 1u : 0u;
-  } else if constexpr (OP == O_FINAL_EXP_OQ) putq(O, final_exp_oq(mkq(I)));
-  else if constexpr (OP == O_FINAL_EXP_OO) putq(O, final_exp_oo(mkq(I)));
+  } else if constexpr (OP == O_FINAL_EXP_OQ) putq(O, final_exp_lg<on_octet, csqr_on_quad>(mkq(I)));
+  else if constexpr (OP == O_FINAL_EXP_OO) putq(O, final_exp_lg<on_octet, csqr_on_octet>(mkq(I)));
   else if constexpr (OP == G_DBL_Q) putjac(O, fl, jac_dbl_q(mkjac(I)));
   else if constexpr (OP == G_ADD_AFF_Q) putjac(O, fl, jac_add_aff_q(mkjac(I), mkaff(I + 3)));
   else if constexpr (OP == G_ADD_Q) putjac(O, fl, jac_add_q(mkjac(I), mkjac(I + 3)));
   else if constexpr (OP == G_PSI_Q) putjac(O, fl, g2_psi_jac_q(mkjac(I)));
-  else if constexpr (OP == G_MUL_U64_Q) putjac(O, fl, jac_mul_u64_q(mkaff(I), aux));
-  else if constexpr (OP == G_MUL_BP_Q) putjac(O, fl, g2_mul_bp_q(mkaff(I)));
+  else if constexpr (OP == G_MUL_U64_Q) putjac(O, fl, jac_mul_u64_lg<on_quad>(mkaff(I), aux));
+  else if constexpr (OP == G_MUL_BP_Q) putjac(O, fl, g2_mul_bp_lg<on_quad>(mkaff(I)));
   else if constexpr (OP == G_DBL_O) putjac(O, fl, jac_dbl_o(mkjac(I)));
-  else if constexpr (OP == G_MUL_U64_O) putjac(O, fl, jac_mul_u64_o(mkaff(I), aux));
-  else if constexpr (OP == G_MUL_BP_O) putjac(O, fl, g2_mul_bp_o(mkaff(I)));
+  else if constexpr (OP == G_MUL_U64_O) putjac(O, fl, jac_mul_u64_lg<on_octet>(mkaff(I), aux));
+  else if constexpr (OP == G_MUL_BP_O) putjac(O, fl, g2_mul_bp_lg<on_octet>(mkaff(I)));
   else if constexpr (OP == M_QUAD) {
     const bool active = ((aux >> (qd_hi() ? 1 : 0)) & 1u) != 0;
     bool degen = false;
@@ -273,10 +277,10 @@ __device__ __forceinline__ void probe(const fp_t* I, uint64_t aux, fp_t* O, uint
     fl = degen ? 1u : 0u;
   } else if constexpr (OP == M_Q1) {
     bool degen = false;
-    putq(O, miller_loop_q1(mkaff(I), mkg1(I + 2), degen));
+    putq(O, miller_loop_lg<on_quad>(mkaff(I), mkg1(I + 2), degen));
     fl = degen ? 1u : 0u;
   } else if constexpr (OP == M_O1) {
-    const fq12_ml r = miller_loop_o1_run(mkaff(I), mkg1(I + 2));
+    const fq12_ml r = miller_loop_lg_run<on_octet>(mkaff(I), mkg1(I + 2));
     putq(O, r.f);
     fl = r.degenerate ? 1u : 0u;
   }

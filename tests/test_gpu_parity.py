@@ -1336,7 +1336,8 @@ gb = json.load(open(os.path.join(root, "tests", "golden", "bls_golden_batches.js
 tor = json.load(open(os.path.join(root, "tests", "golden", "bls_torsion.json")))
 items = [(c, c["expected"]) for c in gb["verify"] if len(bytes.fromhex(c["message"])) == 32]
 items += [(c, c["expected_pyecc"]) for c in tor["verify"]]
-for n in (len(items), 3000):
+# 1, 9, 17: a lone unit, and a ragged second wave of octets (8 items per wave) and of quads (16)
+for n in (1, 9, 17, len(items), 3000):
     sel = [items[i % len(items)] for i in range(n)]
     got = native.verify_batch(b"".join(bytes.fromhex(c["pubkey"]) for c, _ in sel),
                               b"".join(bytes.fromhex(c["message"]) for c, _ in sel),
@@ -1355,14 +1356,17 @@ print("octet fe ok")
 """
 
 
-@pytest.mark.parametrize("knob", ["BLS381_FE_OCT=2", "BLS381_ML_OCTET=0", "BLS381_HASH_OCT=0"])
+@pytest.mark.parametrize("knob", ["BLS381_FE_OCT=0", "BLS381_FE_OCT=2", "BLS381_ML_OCTET=0", "BLS381_HASH_OCT=0"])
 def test_octet_final_exponentiation_knob(knob):
     """The latency path's non-default layouts, each read once per process (so in a child
     process), give the fixture verdicts for bls_verify batches (one and two values per item) and
-    verify_multiple batches: BLS381_FE_OCT=2 (k_final_exp_verdict_oq<.., 0>: products split over
-    the octet, squarings on quads), BLS381_ML_OCTET=0 (the quad Miller kernels k_miller_verify_o
-    and k_miller_tasks<4> for small nf), BLS381_HASH_OCT=0 (k_hash_g2_q, the cofactor map on
-    quads).  The defaults (FE_OCT=3, ML_OCTET=1, HASH_OCT=1) run in every other test."""
+    verify_multiple batches: BLS381_FE_OCT=0 (k_final_exp_verdict_q, also <2>: the two values per
+    item of a small batch multiplied on the quad), BLS381_FE_OCT=2 (k_final_exp_verdict_oq<.., 0>:
+    products split over the octet, squarings on quads), BLS381_ML_OCTET=0 (the quad Miller kernels
+    k_miller_verify_lg<on_quad> and k_miller_tasks<4> for small nf), BLS381_HASH_OCT=0
+    (k_hash_g2_lg<on_quad>, the cofactor map on quads).  The small batch sizes put a lone unit and a
+    ragged second wave under every store mask.  The defaults (FE_OCT=3, ML_OCTET=1, HASH_OCT=1) run
+    in every other test."""
     import subprocess
     var, val = knob.split("=")
     env = dict(os.environ, **{var: val})

@@ -1,6 +1,7 @@
 // Latency of one compressed-squaring chain for a single item: the quad form (cq_sqr, 4 lanes) against
 // the octet form (co_sqr, 8 lanes), REPS dependent squarings in one wave with every lane active
-// (lanes past the item recompute it), as k_final_exp_verdict_q / _o run them for single calls.
+// (lanes past the item recompute it), as k_final_exp_verdict_q / _oq run them for single calls
+// (csqr_on_quad / csqr_on_octet, bls381_quad.hpp).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I consensus-specs_amd/csrc tools/csqr_lat.hip -o tools/csqr_lat
 #include <hip/hip_runtime.h>
 #include <cstdio>
