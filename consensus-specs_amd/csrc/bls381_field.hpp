@@ -167,6 +167,36 @@ BLS_INLINE fp_t fp_3pm2(const fp_t& X, const fp_t& x, bool minus) {
   return fp_reduce_lc<5>(s);
 }
 
+// Fused combinations: NA added and NS subtracted normalized values (< 2q each) as one limb
+// sum and one reduction.  The offset of NS subtracted values is a multiple of 2q whose limbs
+// 0..12 are >= NS (2^28 - 1) and <= (NS + 1)(2^28 - 1): Q4B (4q), Q8T (8q), Q10F (10q) for NS = 2, 3, 4.
+// Three and four subtractions take 2q more than they cancel: limb 12 has to borrow NS from the
+// top limb, and the extra 2q keeps the top limb >= NS Q2_13, above the subtracted top limbs (with
+// Q4B it is >= -2, fp_sub2's case).  Bounds, for every fused form built on this:
+//   limbs 0..12 <= (NA + NS + 1)(2^28 - 1) <= 2^31 - 8    for NA + NS <= 7
+//   value       <  (NA + offset / 2q) 2q = KMAX 2q        with KMAX <= 8
+template <int NS> BLS_INLINE uint32_t lc_offset(int i) {
+  static_assert(NS >= 2 && NS <= 4, "offsets for two to four subtracted values");
+  return NS == 2 ? Q4B_LIMBS[i] : NS == 3 ? Q8T_LIMBS[i] : Q10F_LIMBS[i];
+}
+constexpr int lc_kmax(int na, int ns) { return na + (ns <= 2 ? ns : ns + 1); }   // value bound in units of 2q
+
+template <int NA, int NS>
+BLS_INLINE fp_t fp_lc(const fp_t* const (&add)[NA], const fp_t* const (&sub)[NS]) {
+  static_assert(NA + NS <= 7 && lc_kmax(NA, NS) <= 8, "fp_reduce_lc's limb and value bounds");
+  uint32_t s[14];
+#pragma unroll
+  for (int i = 0; i < 14; ++i) {
+    uint32_t v = lc_offset<NS>(i);
+#pragma unroll
+    for (int j = 0; j < NA; ++j) v += add[j]->w[i];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) v -= sub[j]->w[i];
+    s[i] = v;
+  }
+  return fp_reduce_lc<lc_kmax(NA, NS)>(s);
+}
+
 // lazy sum for a multiplication operand only: limbs < 2^29, value < 4q
 BLS_INLINE fp_t fp_add_lazy(const fp_t& a, const fp_t& b) {
   fp_t r;
@@ -933,6 +963,59 @@ BLS_INLINE fp2_t fp2_add_mul_xi(const fp2_t& a, const fp2_t& b) {
 BLS_INLINE fp2_t fp2_sub2(const fp2_t& a, const fp2_t& b, const fp2_t& c) {
   fp2_t r; r.c0 = fp_sub2(a.c0, b.c0, c.c0); r.c1 = fp_sub2(a.c1, b.c1, c.c1); return r;
 }
+// Fused tower combinations (fp_lc): each returns the limbs the chain of the forms above returns,
+// because every reduction yields the unique representative in [0, 2q).  (NA, NS) -> KMAX per
+// coefficient; the lane-pair forms (bls381_pair.hpp) compute c0 on the even lane, c1 on the odd.
+// a + xi (m - b - c): c0 = a0 + m0 + b1 + c1 - b0 - c0 - m1 (4, 3) -> 8; c1 = a1 + m0 + m1 - b0 - b1 - c0 - c1 (3, 4) -> 8
+BLS_INLINE fp2_t fp2_add_xi_sub2(const fp2_t& a, const fp2_t& m, const fp2_t& b, const fp2_t& c) {
+  fp2_t r;
+  r.c0 = fp_lc({&a.c0, &m.c0, &b.c1, &c.c1}, {&b.c0, &c.c0, &m.c1});
+  r.c1 = fp_lc({&a.c1, &m.c0, &m.c1}, {&b.c0, &b.c1, &c.c0, &c.c1});
+  return r;
+}
+// (m - a - b) + xi c: c0 = m0 + c0 - a0 - b0 - c1 (2, 3) -> 6; c1 = m1 + c0 + c1 - a1 - b1 (3, 2) -> 5
+BLS_INLINE fp2_t fp2_sub2_add_xi(const fp2_t& m, const fp2_t& a, const fp2_t& b, const fp2_t& c) {
+  fp2_t r;
+  r.c0 = fp_lc({&m.c0, &c.c0}, {&a.c0, &b.c0, &c.c1});
+  r.c1 = fp_lc({&m.c1, &c.c0, &c.c1}, {&a.c1, &b.c1});
+  return r;
+}
+// m - a - b + c: (2, 2) -> 4
+BLS_INLINE fp2_t fp2_sub2_add(const fp2_t& m, const fp2_t& a, const fp2_t& b, const fp2_t& c) {
+  fp2_t r;
+  r.c0 = fp_lc({&m.c0, &c.c0}, {&a.c0, &b.c0});
+  r.c1 = fp_lc({&m.c1, &c.c1}, {&a.c1, &b.c1});
+  return r;
+}
+// t - a - xi b: c0 = t0 + b1 - a0 - b0 (2, 2) -> 4; c1 = t1 - a1 - b0 - b1 (1, 3) -> 5
+BLS_INLINE fp2_t fp2_sub_sub_xi(const fp2_t& t, const fp2_t& a, const fp2_t& b) {
+  fp2_t r;
+  r.c0 = fp_lc({&t.c0, &b.c1}, {&a.c0, &b.c0});
+  r.c1 = fp_lc({&t.c1}, {&a.c1, &b.c0, &b.c1});
+  return r;
+}
+// x - y - 2z: (1, 3) -> 5, and 2 (x - y - z): (2, 4) -> 7 (G1 and G2 point formulas)
+BLS_INLINE fp_t fp_sub_sub_dbl(const fp_t& x, const fp_t& y, const fp_t& z) { return fp_lc({&x}, {&y, &z, &z}); }
+BLS_INLINE fp_t fp_dbl_sub2(const fp_t& x, const fp_t& y, const fp_t& z) { return fp_lc({&x, &x}, {&y, &y, &z, &z}); }
+BLS_INLINE fp2_t fp2_sub_sub_dbl(const fp2_t& x, const fp2_t& y, const fp2_t& z) {
+  fp2_t r; r.c0 = fp_sub_sub_dbl(x.c0, y.c0, z.c0); r.c1 = fp_sub_sub_dbl(x.c1, y.c1, z.c1); return r;
+}
+BLS_INLINE fp2_t fp2_dbl_sub2(const fp2_t& x, const fp2_t& y, const fp2_t& z) {
+  fp2_t r; r.c0 = fp_dbl_sub2(x.c0, y.c0, z.c0); r.c1 = fp_dbl_sub2(x.c1, y.c1, z.c1); return r;
+}
+// 3a + xi b - 2c: c0 = 3 a0 + b0 - b1 - 2 c0 (4, 3) -> 8; c1 = 3 a1 + b0 + b1 - 2 c1 (5, 2) -> 7 (cyc_decompress)
+BLS_INLINE fp2_t fp2_3a_xi_b_m2c(const fp2_t& a, const fp2_t& b, const fp2_t& c) {
+  fp2_t r;
+  r.c0 = fp_lc({&a.c0, &a.c0, &a.c0, &b.c0}, {&b.c1, &c.c0, &c.c0});
+  r.c1 = fp_lc({&a.c1, &a.c1, &a.c1, &b.c0, &b.c1}, {&c.c1, &c.c1});
+  return r;
+}
+// 2a + b - 3c: (3, 3) -> 7 (cyc_decompress)
+BLS_INLINE fp_t fp_2a_b_m3c(const fp_t& a, const fp_t& b, const fp_t& c) { return fp_lc({&a, &a, &b}, {&c, &c, &c}); }
+BLS_INLINE fp2_t fp2_2a_b_m3c(const fp2_t& a, const fp2_t& b, const fp2_t& c) {
+  fp2_t r; r.c0 = fp_2a_b_m3c(a.c0, b.c0, c.c0); r.c1 = fp_2a_b_m3c(a.c1, b.c1, c.c1); return r;
+}
+
 // 3X - 2x and 3X + 2x
 BLS_INLINE fp2_t fp2_3m2(const fp2_t& X, const fp2_t& x) {
   fp2_t r; r.c0 = fp_3m2(X.c0, x.c0); r.c1 = fp_3m2(X.c1, x.c1); return r;
@@ -1001,9 +1084,10 @@ BLS_INLINE fp6_g<E> fp6_mul_inl(const fp6_g<E>& a, const fp6_g<E>& b) {
   const E t1 = fp2_mul(a.c1, b.c1);
   const E t2 = fp2_mul(a.c2, b.c2);
   fp6_g<E> r;
-  r.c0 = fp2_add_mul_xi(t0, fp2_sub2(fp2_mul(fp2_add_lazy(a.c1, a.c2), fp2_add_lazy(b.c1, b.c2)), t1, t2));
-  r.c1 = fp2_add_mul_xi(fp2_sub2(fp2_mul(fp2_add_lazy(a.c0, a.c1), fp2_add_lazy(b.c0, b.c1)), t0, t1), t2);
-  r.c2 = fp2_add(fp2_sub2(fp2_mul(fp2_add_lazy(a.c0, a.c2), fp2_add_lazy(b.c0, b.c2)), t0, t2), t1);
+  // one reduction per output coefficient (the fused forms' bounds: fp2_add_xi_sub2 and below)
+  r.c0 = fp2_add_xi_sub2(t0, fp2_mul(fp2_add_lazy(a.c1, a.c2), fp2_add_lazy(b.c1, b.c2)), t1, t2);
+  r.c1 = fp2_sub2_add_xi(fp2_mul(fp2_add_lazy(a.c0, a.c1), fp2_add_lazy(b.c0, b.c1)), t0, t1, t2);
+  r.c2 = fp2_sub2_add(fp2_mul(fp2_add_lazy(a.c0, a.c2), fp2_add_lazy(b.c0, b.c2)), t0, t2, t1);
   return r;
 }
 
@@ -1086,7 +1170,10 @@ BLS_INLINE fp12_g<E> fp12_sqr_inl(const fp12_g<E>& f) {
   const fp6_g<E> ab = fp6_mul_inl(f.c0, f.c1);
   const fp6_g<E> t = fp6_mul_inl(fp6_add(f.c0, f.c1), fp6_add_mul_by_v(f.c0, f.c1));
   fp12_g<E> r;
-  r.c0 = fp6_sub2(t, ab, fp6_mul_by_v(ab));
+  // t - ab - v ab: v ab = (xi ab2, ab0, ab1)
+  r.c0.c0 = fp2_sub_sub_xi(t.c0, ab.c0, ab.c2);
+  r.c0.c1 = fp2_sub2(t.c1, ab.c1, ab.c0);
+  r.c0.c2 = fp2_sub2(t.c2, ab.c2, ab.c1);
   r.c1 = fp6_dbl(ab);
   return r;
 }

@@ -732,19 +732,19 @@ __device__ __forceinline__ fp12p_t fp12_mul_by_line_pair_lds(const fp12p_t& f, c
     const fp2p_t t0 = fp2_mul(a.c0, ml_lds_c(col, 0));
     const fp2p_t t1 = fp2_mul(a.c1, ml_lds_c(col, 1));
     const fp2p_t t2 = fp2_mul(a.c2, ml_lds_c(col, 2));
-    aP.c0 = fp2_add_mul_xi(t0, fp2_sub2(fp2_mul(fp2_add_lazy(a.c1, a.c2),
-                                                fp2_add_lazy(ml_lds_c(col, 1), ml_lds_c(col, 2))), t1, t2));
-    aP.c1 = fp2_add_mul_xi(fp2_sub2(fp2_mul(fp2_add_lazy(a.c0, a.c1),
-                                            fp2_add_lazy(ml_lds_c(col, 0), ml_lds_c(col, 1))), t0, t1), t2);
-    aP.c2 = fp2_add(fp2_sub2(fp2_mul(fp2_add_lazy(a.c0, a.c2),
-                                     fp2_add_lazy(ml_lds_c(col, 0), ml_lds_c(col, 2))), t0, t2), t1);
+    aP.c0 = fp2_add_xi_sub2(t0, fp2_mul(fp2_add_lazy(a.c1, a.c2),
+                                        fp2_add_lazy(ml_lds_c(col, 1), ml_lds_c(col, 2))), t1, t2);
+    aP.c1 = fp2_sub2_add_xi(fp2_mul(fp2_add_lazy(a.c0, a.c1),
+                                    fp2_add_lazy(ml_lds_c(col, 0), ml_lds_c(col, 1))), t0, t1, t2);
+    aP.c2 = fp2_sub2_add(fp2_mul(fp2_add_lazy(a.c0, a.c2),
+                                 fp2_add_lazy(ml_lds_c(col, 0), ml_lds_c(col, 2))), t0, t2, t1);
   }
   fp6p_t bQ;
   {
     const fp2p_t t1 = fp2_mul(b.c1, ml_lds_c(col, 3));
     const fp2p_t t2 = fp2_mul(b.c2, ml_lds_c(col, 4));
-    bQ.c0 = fp2_mul_xi(fp2_sub2(fp2_mul(fp2_add_lazy(b.c1, b.c2), fp2_add_lazy(ml_lds_c(col, 3), ml_lds_c(col, 4))),
-                                t1, t2));
+    bQ.c0 = fp2_add_xi_sub2(e2_zero<fp2p_t>(),
+                            fp2_mul(fp2_add_lazy(b.c1, b.c2), fp2_add_lazy(ml_lds_c(col, 3), ml_lds_c(col, 4))), t1, t2);
     bQ.c1 = fp2_add_mul_xi(fp2_mul(b.c0, ml_lds_c(col, 3)), t2);
     bQ.c2 = fp2_add(fp2_mul(b.c0, ml_lds_c(col, 4)), t1);
   }

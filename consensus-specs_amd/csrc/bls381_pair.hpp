@@ -221,6 +221,66 @@ __device__ __forceinline__ fp2p_t fp2_add_mul_xi(const fp2p_t& a, const fp2p_t& 
 __device__ __forceinline__ fp2p_t fp2_sub2(const fp2p_t& a, const fp2p_t& b, const fp2p_t& c) {
   return pr_make(fp_sub2(a.v, b.v, c.v));
 }
+// Fused tower combinations: the one-lane forms of bls381_field.hpp with coefficient c0's sum on
+// the even lane and c1's on the odd one; the partner's terms come by DPP.  Each lane's sum is the
+// one-lane coefficient's term for term, so its (NA, NS) bounds are the ones stated there: the
+// even lane's offset is the one for c0's subtracted values, the odd lane's the one for c1's.
+// a + xi (m - b - c) -- lane 0: a + m + bo + co - b - c - mo + 8q; lane 1: a + m + mo - b - c - bo - co + 10q
+__device__ __forceinline__ fp2p_t fp2_add_xi_sub2(const fp2p_t& a, const fp2p_t& m, const fp2p_t& b, const fp2p_t& c) {
+  const bool odd = pr_odd();
+  // u = m - b - c limb-wise mod 2^32 is the same expression on both lanes, so one exchange brings the
+  // partner's three terms; the lane's whole sum below is not negative
+  fp_t u;
+#pragma unroll
+  for (int i = 0; i < 14; ++i) u.w[i] = m.v.w[i] - b.v.w[i] - c.v.w[i];
+  const fp_t uo = pr_dpp<DPP_SWAP>(u);
+  uint32_t s[14];
+#pragma unroll
+  for (int i = 0; i < 14; ++i) s[i] = a.v.w[i] + u.w[i] + (odd ? Q10F_LIMBS[i] + uo.w[i] : Q8T_LIMBS[i] - uo.w[i]);
+  return pr_make(fp_reduce_lc<8>(s));
+}
+// (m - a - b) + xi c -- lane 0: m + c - a - b - co + 8q; lane 1: m + c + co - a - b + 4q
+__device__ __forceinline__ fp2p_t fp2_sub2_add_xi(const fp2p_t& m, const fp2p_t& a, const fp2p_t& b, const fp2p_t& c) {
+  const bool odd = pr_odd();
+  const fp_t co = pr_dpp<DPP_SWAP>(c.v);
+  uint32_t s[14];
+#pragma unroll
+  for (int i = 0; i < 14; ++i)
+    s[i] = m.v.w[i] + c.v.w[i] - a.v.w[i] - b.v.w[i] + (odd ? Q4B_LIMBS[i] + co.w[i] : Q8T_LIMBS[i] - co.w[i]);
+  return pr_make(fp_reduce_lc<6>(s));
+}
+__device__ __forceinline__ fp2p_t fp2_sub2_add(const fp2p_t& m, const fp2p_t& a, const fp2p_t& b, const fp2p_t& c) {
+  return pr_make(fp_lc({&m.v, &c.v}, {&a.v, &b.v}));
+}
+// t - a - xi b -- lane 0: t + bo - a - b + 4q; lane 1: t - a - b - bo + 8q
+__device__ __forceinline__ fp2p_t fp2_sub_sub_xi(const fp2p_t& t, const fp2p_t& a, const fp2p_t& b) {
+  const bool odd = pr_odd();
+  const fp_t bo = pr_dpp<DPP_SWAP>(b.v);
+  uint32_t s[14];
+#pragma unroll
+  for (int i = 0; i < 14; ++i)
+    s[i] = t.v.w[i] - a.v.w[i] - b.v.w[i] + (odd ? Q8T_LIMBS[i] - bo.w[i] : Q4B_LIMBS[i] + bo.w[i]);
+  return pr_make(fp_reduce_lc<5>(s));
+}
+__device__ __forceinline__ fp2p_t fp2_sub_sub_dbl(const fp2p_t& x, const fp2p_t& y, const fp2p_t& z) {
+  return pr_make(fp_sub_sub_dbl(x.v, y.v, z.v));
+}
+__device__ __forceinline__ fp2p_t fp2_dbl_sub2(const fp2p_t& x, const fp2p_t& y, const fp2p_t& z) {
+  return pr_make(fp_dbl_sub2(x.v, y.v, z.v));
+}
+// 3a + xi b - 2c -- lane 0: 3a + b - bo - 2c + 8q; lane 1: 3a + b + bo - 2c + 4q
+__device__ __forceinline__ fp2p_t fp2_3a_xi_b_m2c(const fp2p_t& a, const fp2p_t& b, const fp2p_t& c) {
+  const bool odd = pr_odd();
+  const fp_t bo = pr_dpp<DPP_SWAP>(b.v);
+  uint32_t s[14];
+#pragma unroll
+  for (int i = 0; i < 14; ++i)
+    s[i] = 3u * a.v.w[i] + b.v.w[i] - (c.v.w[i] << 1) + (odd ? Q4B_LIMBS[i] + bo.w[i] : Q8T_LIMBS[i] - bo.w[i]);
+  return pr_make(fp_reduce_lc<8>(s));
+}
+__device__ __forceinline__ fp2p_t fp2_2a_b_m3c(const fp2p_t& a, const fp2p_t& b, const fp2p_t& c) {
+  return pr_make(fp_2a_b_m3c(a.v, b.v, c.v));
+}
 __device__ __forceinline__ fp2p_t fp2_3m2(const fp2p_t& X, const fp2p_t& x) { return pr_make(fp_3m2(X.v, x.v)); }
 __device__ __forceinline__ fp2p_t fp2_3p2(const fp2p_t& X, const fp2p_t& x) { return pr_make(fp_3p2(X.v, x.v)); }
 __device__ __forceinline__ fp2p_t fp2_3pm2(const fp2p_t& X, const fp2p_t& x, bool minus) {
@@ -446,6 +506,8 @@ __device__ __forceinline__ fp2p_t f_sqr(const fp2p_t& a) { return fp2_sqr(a); }
 __device__ __forceinline__ fp2p_t f_dbl(const fp2p_t& a) { return fp2_dbl(a); }
 __device__ __forceinline__ fp2p_t f_neg(const fp2p_t& a) { return fp2_neg(a); }
 __device__ __forceinline__ fp2p_t f_sub2(const fp2p_t& a, const fp2p_t& b, const fp2p_t& c) { return fp2_sub2(a, b, c); }
+__device__ __forceinline__ fp2p_t f_sub_sub_dbl(const fp2p_t& x, const fp2p_t& y, const fp2p_t& z) { return fp2_sub_sub_dbl(x, y, z); }
+__device__ __forceinline__ fp2p_t f_dbl_sub2(const fp2p_t& x, const fp2p_t& y, const fp2p_t& z) { return fp2_dbl_sub2(x, y, z); }
 __device__ __forceinline__ fp2p_t f_mul_small(const fp2p_t& a, int k) { return fp2_mul_small(a, k); }
 __device__ __forceinline__ bool f_is_zero(const fp2p_t& a) { return fp2_is_zero(a); }
 __device__ __forceinline__ bool f_eq(const fp2p_t& a, const fp2p_t& b) { return fp2_eq(a, b); }

@@ -72,7 +72,7 @@ BLS_DEV_INLINE void line_add(g2_proj<E>& T, const aff_t<E>& Q, const g1_line_pre
   const E vv = fp2_sqr(v);
   const E vvv = fp2_mul(vv, v);
   const E vvX = fp2_mul(vv, T.x);
-  const E A = fp2_sub2(fp2_mul(fp2_sqr(u), T.z), vvv, fp2_dbl(vvX));
+  const E A = fp2_sub_sub_dbl(fp2_mul(fp2_sqr(u), T.z), vvv, vvX);
   g2_proj<E> R;
   R.x = fp2_mul(v, A);
   R.y = fp2_sub(fp2_mul(u, fp2_sub(vvX, A)), fp2_mul(vvv, T.y));
@@ -114,7 +114,7 @@ BLS_INLINE fp12_g<E> fp12_mul_by_line_pair_inl(const fp12_g<E>& f, const fp12_g<
   {
     const E t1 = fp2_mul(b.c1, L.c1.c1);
     const E t2 = fp2_mul(b.c2, L.c1.c2);
-    bQ.c0 = fp2_mul_xi(fp2_sub2(fp2_mul(fp2_add_lazy(b.c1, b.c2), fp2_add_lazy(L.c1.c1, L.c1.c2)), t1, t2));
+    bQ.c0 = fp2_add_xi_sub2(e2_zero<E>(), fp2_mul(fp2_add_lazy(b.c1, b.c2), fp2_add_lazy(L.c1.c1, L.c1.c2)), t1, t2);
     bQ.c1 = fp2_add_mul_xi(fp2_mul(b.c0, L.c1.c1), t2);
     bQ.c2 = fp2_add(fp2_mul(b.c0, L.c1.c2), t1);
   }
@@ -292,11 +292,11 @@ BLS_INLINE cyc_bc<E> cyc_csqr(const cyc_bc<E>& g) {
 // the full element from (g2..g5) and 1 / (4 g2)
 template <class E>
 BLS_INLINE fp12_g<E> cyc_decompress(const cyc_bc<E>& g, const E& inv4g2) {
-  const E num = fp2_sub2(fp2_add_mul_xi(fp2_mul_small(fp2_sqr(g.g4), 3), fp2_sqr(g.g5)), g.g3, g.g3);
+  const E num = fp2_3a_xi_b_m2c(fp2_sqr(g.g4), fp2_sqr(g.g5), g.g3);
   const E b1 = fp2_mul(num, inv4g2);
-  const E u = fp2_sub(fp2_add(fp2_dbl(fp2_sqr(b1)), fp2_mul(g.g2, g.g5)), fp2_mul_small(fp2_mul(g.g3, g.g4), 3));
+  const E u = fp2_2a_b_m3c(fp2_sqr(b1), fp2_mul(g.g2, g.g5), fp2_mul(g.g3, g.g4));
   fp12_g<E> f;
-  f.c0.c0 = fp2_add(fp2_mul_xi(u), e2_one<E>());
+  f.c0.c0 = fp2_add_mul_xi(e2_one<E>(), u);
   f.c0.c1 = g.g4; f.c0.c2 = g.g3;
   f.c1.c0 = g.g2; f.c1.c1 = b1; f.c1.c2 = g.g5;
   return f;

@@ -26,7 +26,9 @@
 // Probes (slots in -> slots out; an Fp12 is 6 slots on a pair, 3 on a quad):
 //   pair Fp2    P_MUL (a, b -> fp2_mul, the fp2p_mul_call path, lazy operands allowed), P_SQR,
 //               P_CONJ, P_MUL_XI, P_ADD_MUL_XI, P_SUB2, P_3PM2 (aux: minus), P_MUL_SMALL (aux: k),
-//               P_INV, P_PRED (flag: fp2_is_zero(a) | fp2_eq(a, b) << 1 | pr_both(a0 == b0) << 2)
+//               P_INV, P_PRED (flag: fp2_is_zero(a) | fp2_eq(a, b) << 1 | pr_both(a0 == b0) << 2),
+//               the fused combinations P_ADD_XI_SUB2, P_SUB2_ADD_XI, P_SUB2_ADD (4 operands each),
+//               P_SUB_SUB_XI, P_SUB_SUB_DBL, P_DBL_SUB2, P_3A_XI_B_M2C, P_2A_B_M3C (3 each)
 //   pair Fp12   P12_MUL, P12_SQR, P12_CYC_SQR, P12_MUL_BY_LINE, P12_FROB (p = 1, 2, 3), P12_INV,
 //               P_CSQR (cyc_csqr on (g2..g5), aux: count), P12_FINAL_EXP (final_exp, the chain with
 //               the exact fallback), P12_FINAL_EXP_NOFB (final_exp_ct<.., 0>, k_final_exp_verdict's:
@@ -103,7 +105,15 @@ namespace {
   X(G_MUL_BP_O, 8, 4, 2, 3, 1)         \
   X(M_QUAD, 4, 4, 4, 3, 1)             \
   X(M_Q1, 4, 4, 4, 3, 1)               \
-  X(M_O1, 8, 4, 4, 3, 1)
+  X(M_O1, 8, 4, 4, 3, 1)               \
+  X(P_ADD_XI_SUB2, 2, 2, 4, 1, 0)      \
+  X(P_SUB2_ADD_XI, 2, 2, 4, 1, 0)      \
+  X(P_SUB2_ADD, 2, 2, 4, 1, 0)         \
+  X(P_SUB_SUB_XI, 2, 2, 3, 1, 0)       \
+  X(P_SUB_SUB_DBL, 2, 2, 3, 1, 0)      \
+  X(P_DBL_SUB2, 2, 2, 3, 1, 0)         \
+  X(P_3A_XI_B_M2C, 2, 2, 3, 1, 0)      \
+  X(P_2A_B_M3C, 2, 2, 3, 1, 0)
 
 enum dc_op : int {
 #define X(name, g, gin, nin, nout, pad) name,
@@ -283,7 +293,17 @@ __device__ __forceinline__ void probe(const fp_t* I, uint64_t aux, fp_t* O, uint
     const fq12_ml r = miller_loop_lg_run<on_octet>(mkaff(I), mkg1(I + 2));
     putq(O, r.f);
     fl = r.degenerate ? 1u : 0u;
-  }
+  } else if constexpr (OP == P_ADD_XI_SUB2)
+    O[0] = fp2_add_xi_sub2(pr_make(I[0]), pr_make(I[1]), pr_make(I[2]), pr_make(I[3])).v;
+  else if constexpr (OP == P_SUB2_ADD_XI)
+    O[0] = fp2_sub2_add_xi(pr_make(I[0]), pr_make(I[1]), pr_make(I[2]), pr_make(I[3])).v;
+  else if constexpr (OP == P_SUB2_ADD)
+    O[0] = fp2_sub2_add(pr_make(I[0]), pr_make(I[1]), pr_make(I[2]), pr_make(I[3])).v;
+  else if constexpr (OP == P_SUB_SUB_XI) O[0] = fp2_sub_sub_xi(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
+  else if constexpr (OP == P_SUB_SUB_DBL) O[0] = fp2_sub_sub_dbl(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
+  else if constexpr (OP == P_DBL_SUB2) O[0] = fp2_dbl_sub2(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
+  else if constexpr (OP == P_3A_XI_B_M2C) O[0] = fp2_3a_xi_b_m2c(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
+  else if constexpr (OP == P_2A_B_M3C) O[0] = fp2_2a_b_m3c(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
 }
 
 // one wave per block; L lanes in all (a multiple of 64), the first `live` of them store

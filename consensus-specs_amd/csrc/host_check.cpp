@@ -156,6 +156,47 @@ int hc_raw_fp2(int op, const uint32_t* in, uint64_t aux, uint32_t* out) {
     }
   }
 }
+// The fused tower combinations on raw Fp2 operands in argument order: op 0 fp2_add_xi_sub2 (a, m, b, c),
+// 1 fp2_sub2_add_xi (m, a, b, c), 2 fp2_sub2_add (m, a, b, c), 3 fp2_sub_sub_xi (t, a, b),
+// 4 fp2_sub_sub_dbl (x, y, z), 5 fp2_dbl_sub2 (x, y, z), 6 fp2_3a_xi_b_m2c (a, b, c), 7 fp2_2a_b_m3c (a, b, c).
+// Returns the number of operands read, -1 for an unknown op.
+int hc_raw_fp2_lc(int op, const uint32_t* in, uint32_t* out) {
+  if (op < 0 || op > 7) return -1;
+  const int n = op <= 2 ? 4 : 3;
+  fp2_t x[4];
+  for (int j = 0; j < n; ++j) x[j] = rw2(in);
+  switch (op) {
+    case 0: ww2(out, fp2_add_xi_sub2(x[0], x[1], x[2], x[3])); break;
+    case 1: ww2(out, fp2_sub2_add_xi(x[0], x[1], x[2], x[3])); break;
+    case 2: ww2(out, fp2_sub2_add(x[0], x[1], x[2], x[3])); break;
+    case 3: ww2(out, fp2_sub_sub_xi(x[0], x[1], x[2])); break;
+    case 4: ww2(out, fp2_sub_sub_dbl(x[0], x[1], x[2])); break;
+    case 5: ww2(out, fp2_dbl_sub2(x[0], x[1], x[2])); break;
+    case 6: ww2(out, fp2_3a_xi_b_m2c(x[0], x[1], x[2])); break;
+    default: ww2(out, fp2_2a_b_m3c(x[0], x[1], x[2])); break;
+  }
+  return n;
+}
+// op 0 fp6_mul (a, b: 3 Fp2 each -> 3 Fp2), 1 fp12_mul_by_line_pair_inl (f, then the lines c0, c1, c2 and
+// d0, d1, d2 -> f (l l'), 6 Fp2), 2 line_pair_product alone (c0..d2 -> 6 Fp2)
+int hc_raw_tower(int op, const uint32_t* in, uint32_t* out) {
+  if (op == 0) {
+    fp6_t a, b;
+    a.c0 = rw2(in); a.c1 = rw2(in); a.c2 = rw2(in);
+    b.c0 = rw2(in); b.c1 = rw2(in); b.c2 = rw2(in);
+    const fp6_t r = fp6_mul(a, b);
+    ww2(out, r.c0); ww2(out, r.c1); ww2(out, r.c2);
+    return 0;
+  }
+  if (op != 1 && op != 2) return -1;
+  fp12_t f = fp12_one<fp2_t>();
+  if (op == 1) f = rw12(in);
+  fp2_t l[6];
+  for (int j = 0; j < 6; ++j) l[j] = rw2(in);
+  const fp12_t L = line_pair_product(l[0], l[1], l[2], l[3], l[4], l[5]);
+  ww12(out, op == 1 ? fp12_mul_by_line_pair_inl(f, L) : L);
+  return 0;
+}
 // op 0 mul, 1 sqr, 2 cyclotomic sqr, 3 mul_by_line (f, c0, c1, c2), 4 frob (aux = p), 5 inv, 6 final_exp,
 // 7 cyc_exp_x, 8 cyc_exp_x_gs, 9 cyc_decompress (g2..g5, 1 / (4 g2))
 int hc_raw_fp12(int op, const uint32_t* in, uint64_t aux, uint32_t* out) {
