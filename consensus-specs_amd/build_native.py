@@ -3,6 +3,7 @@
 * lib/libbls381.so            -- the product: hipcc --offload-arch=gfx950, C ABI of include/bls381.h
 * lib/libbls381_hostcheck.so  -- test infrastructure: g++ build of the same arithmetic headers
 * lib/libbls381_devcheck.so   -- test infrastructure: gfx950 probe kernels over the lane-pair / quad / octet headers
+* lib/libbls381_rbcheck.so    -- test infrastructure: the randomized batch's own scalar-side kernels, every intermediate handed back
 * tools/valu_peak             -- integer-VALU peak microbenchmark (roofline denominator)
 """
 import os
@@ -46,6 +47,12 @@ def build_devcheck(force=False):
     """The device check library (csrc/dev_check.hip): the product's hipcc flags, no extra defines."""
     deps = [os.path.join(CSRC, f) for f in ["dev_check.hip"] + HEADERS if f != "bls381_kernels.hpp"]
     return _hipcc_shared(os.path.join(LIB, "libbls381_devcheck.so"), ["dev_check.hip"], deps, force)
+
+
+def build_rbcheck(force=False):
+    """The randomized-batch probe library (csrc/rb_check.hip): the product's kernels header and hipcc flags."""
+    deps = [os.path.join(CSRC, f) for f in ["rb_check.hip"] + HEADERS] + [os.path.join(INC, "bls381.h")]
+    return _hipcc_shared(os.path.join(LIB, "libbls381_rbcheck.so"), ["rb_check.hip"], deps, force)
 
 
 def _hipcc_shared(out, sources, deps, force=False, extra=()):
@@ -136,3 +143,4 @@ if __name__ == "__main__":
     build_valu_peak(force)
     build_hip(force)
     build_devcheck(force)
+    build_rbcheck(force)

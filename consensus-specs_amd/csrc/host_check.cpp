@@ -230,6 +230,21 @@ int hc_raw_g2(int op, const uint32_t* in, uint64_t aux, uint32_t* out) {
     default: return wwjac(out, g2_mul_bp(rwaff(in)));
   }
 }
+// jac_mul_2x32 (the randomized batch's joint 32-bit ladder) on raw limbs: [k0] a + [k1] s, Jacobian out.
+// group 0: E(Fp), in = a.x, a.y, s.x, s.y (4 Fp) -> X, Y, Z (3 Fp); group 1: E'(Fp2), in = 8 Fp -> 6 Fp.
+// Returns whether the result is the point at infinity, -1 for an unknown group.
+int hc_raw_mul_2x32(int group, const uint32_t* in, uint32_t k0, uint32_t k1, uint32_t* out) {
+  if (group == 0) {
+    aff_t<fp_t> a, s;
+    a.x = rw(in); a.y = rw(in); s.x = rw(in); s.y = rw(in);
+    const jac_t<fp_t> r = jac_mul_2x32(a, s, k0, k1);
+    ww(out, r.x); ww(out, r.y); ww(out, r.z);
+    return jac_is_inf(r) ? 1 : 0;
+  }
+  if (group != 1) return -1;
+  const aff_t<fp2_t> a = rwaff(in), s = rwaff(in);
+  return wwjac(out, jac_mul_2x32(a, s, k0, k1));
+}
 // Miller loop of n <= 2 pairs, each Q (x, y in Fp2) then P (x, y in Fp); returns degenerate
 int hc_raw_miller(int n, const uint32_t* in, uint32_t* out) {
   aff_t<fp2_t> Q[2];
