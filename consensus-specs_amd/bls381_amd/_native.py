@@ -104,6 +104,16 @@ _SIGS = {
     "bls381_registry_process_deposits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p,
                                                                ctypes.c_uint64, _u8p, _u8p, ctypes.c_int, _u8p, _u8p,
                                                                ctypes.POINTER(ctypes.c_int64), _u8p, _u8p]),
+    "bls381_shuffle_workspace_size": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]),
+    "bls381_shuffle": (ctypes.c_int, [ctypes.c_uint64, _u8p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _u8p,
+                                      _u8p]),
+    "bls381_shuffle_device": (ctypes.c_int, [ctypes.c_uint64, _u8p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
+                                             _u8p, _u8p, _u8p, _u8p]),
+    "bls381_attesting_entries_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_size_t]),
+    "bls381_attesting_entries": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_size_t,
+                                                _u8p, _u8p, _u8p, ctypes.c_size_t]),
+    "bls381_attesting_entries_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p,
+                                                       ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p, _u8p]),
     "bls381_registry_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     "bls381_registry_destroy": (None, [ctypes.c_void_p]),
     "bls381_registry_size": (ctypes.c_size_t, [ctypes.c_void_p]),

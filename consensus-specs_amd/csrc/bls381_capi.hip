@@ -1994,6 +1994,213 @@ int bls381_registry_process_deposits(bls381_registry* reg, size_t n, const uint8
   });
 }
 
+// ---- committees: get_shuffled_index / compute_committee and convert_to_indexed
+// BLS381_SHUFFLE_PATH (measurement knob): 1 = always the direct path, 2 = always the table path,
+// 0 (default) = by the rule below
+static int shuffle_path_knob() {
+  static const int v = env_knob("BLS381_SHUFFLE_PATH", 0);
+  return v;
+}
+// Direct (every position hashes its own source block each round: rounds * count hashes, `rounds`
+// of them in sequence on each lane) only where the table (rounds * ceil(n / 256) hashes, all
+// independent) is both more hashes and a long build: count <= ceil(n / 256) and a list of at least
+// SHUFFLE_DIRECT_MIN_BLOCKS blocks.  Measured at 90 rounds (profiles/shuffle_bench.json, kernel
+// ms, direct / table): a window of 64 takes 0.41 / 0.09 at n = 2^20, 0.41 / 0.17 at 2^22,
+// 0.41 / 0.53 at 2^24 and 0.40 / 1.91 at 2^26 -- the direct path's time is its 90 hashes in
+// sequence whatever the list, the table's grows with the list -- and the window
+// count = ceil(n / 256) takes 0.51 / 0.09 at 2^20, 0.66 / 0.54 at 2^24 and 1.80 / 2.07 at 2^26.
+constexpr size_t SHUFFLE_DIRECT_MIN_BLOCKS = 65536;   // n > 2^24 - 256
+static bool shuffle_direct(uint64_t n, uint64_t count) {
+  const int k = shuffle_path_knob();
+  const size_t blocks = shuffle_blocks(n);
+  return k == 1 || (k != 2 && blocks >= SHUFFLE_DIRECT_MIN_BLOCKS && count <= blocks);
+}
+struct ShuffleWs {
+  uint32_t *pivots, *table;
+};
+static ShuffleWs carve_shuffle(Bump& b, uint64_t n, uint64_t count, uint32_t rounds) {
+  ShuffleWs w;
+  w.pivots = b.take<uint32_t>(SHUFFLE_ROUNDS_MAX + 1);
+  w.table = shuffle_direct(n, count) ? nullptr : b.take<uint32_t>((size_t)rounds * shuffle_blocks(n) * 8);
+  return w;
+}
+static bool shuffle_args_ok(uint64_t n, const uint8_t* seed, uint32_t rounds, uint64_t first, uint64_t count,
+                            const void* out) {
+  if (n > 0xFFFFFFFFull || rounds > SHUFFLE_ROUNDS_MAX || first > n || count > n - first) return false;
+  return count == 0 || (seed && out);
+}
+size_t bls381_shuffle_workspace_size(uint64_t index_count, uint64_t count, uint32_t rounds) {
+  if (index_count > 0xFFFFFFFFull || rounds > SHUFFLE_ROUNDS_MAX || count > index_count) return 0;
+  return carved_bytes([&](Bump& b) { carve_shuffle(b, index_count, count, rounds); });
+}
+
+int bls381_shuffle_device(uint64_t index_count, const uint8_t seed[32], uint32_t rounds, uint64_t first,
+                          uint64_t count, const uint32_t* d_indices, uint32_t* d_out, void* d_workspace,
+                          void* stream) {
+  return guarded([&]() -> int {
+    if (!shuffle_args_ok(index_count, seed, rounds, first, count, d_out) || (count && !d_workspace))
+      return BLS381_EARG;
+    if (count == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_shuffle_workspace_size(index_count, count, rounds));
+    const ShuffleWs w = carve_shuffle(b, index_count, count, rounds);
+    const uint32_t n = (uint32_t)index_count, f = (uint32_t)first;
+    const shuffle_seed sd = shuffle_seed_from_bytes(seed);
+    const dim3 g(grid_for(count)), blk(KBLOCK);
+    LAUNCH("shuffle_pivots", s, dim3(grid_for(rounds)), blk, k_shuffle_pivots, n, sd, rounds, w.pivots);
+    if (w.table) {
+      const size_t blocks = shuffle_blocks(n);
+      LAUNCH("shuffle_table", s, dim3(grid_for((size_t)rounds * blocks)), blk, k_shuffle_table, sd, rounds, blocks, w.table);
+      LAUNCH("shuffle_walk", s, g, blk, k_shuffle_walk, n, rounds, (const uint32_t*)w.pivots, (const uint32_t*)w.table,
+             blocks, f, (size_t)count, d_indices, d_out);
+    } else {
+      LAUNCH("shuffle_direct", s, g, blk, k_shuffle_direct, n, sd, rounds, (const uint32_t*)w.pivots, f, (size_t)count,
+             d_indices, d_out);
+    }
+    return 0;
+  });
+}
+
+int bls381_shuffle(uint64_t index_count, const uint8_t seed[32], uint32_t rounds, uint64_t first, uint64_t count,
+                   const uint32_t* indices, uint32_t* out) {
+  return guarded([&]() -> int {
+    if (!shuffle_args_ok(index_count, seed, rounds, first, count, out)) return BLS381_EARG;
+    if (count == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_shuffle_workspace_size(index_count, count, rounds);
+    uint32_t *d_idx = nullptr, *d_out;
+    uint8_t* d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      if (indices) d_idx = b.take<uint32_t>(index_count);
+      d_out = b.take<uint32_t>(count);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    if (indices) TRY(hc.upload(d_idx, indices, 4 * index_count));
+    TRY(bls381_shuffle_device(index_count, seed, rounds, first, count, d_idx, d_out, d_ws, hc.s));
+    TRY(hc.download(out, d_out, 4 * count));
+    return hc.finish();
+  });
+}
+
+// the attesting-entries workspace: one descriptor per attestation and both bitfield buffers
+struct AttWs {
+  att_desc* desc;
+  uint8_t *agg, *cust;
+};
+static AttWs carve_att(Bump& b, size_t n_att, size_t bitfield_bytes) {
+  AttWs w;
+  w.desc = b.take<att_desc>(n_att);
+  w.agg = b.take<uint8_t>(bitfield_bytes + 1);
+  w.cust = b.take<uint8_t>(bitfield_bytes + 1);
+  return w;
+}
+size_t bls381_attesting_entries_workspace_size(size_t n_att, size_t bitfield_bytes) {
+  return carved_bytes([&](Bump& b) { carve_att(b, n_att, bitfield_bytes); });
+}
+
+// The host half of both forms: verify_bitfield and the popcounts.  Fills h_ok, h_group_key_off and
+// desc; EARG for a committee outside the shuffled list or over MAX_INDICES_PER_ATTESTATION,
+// descending bit offsets, or more members than entries_cap.
+static int att_plan(size_t n_att, const uint32_t* coff, const uint32_t* clen, const uint32_t* boff, const uint8_t* agg,
+                    const uint8_t* cust, size_t n_shuffled, uint32_t* gko, uint8_t* ok, size_t entries_cap,
+                    att_desc* desc) {
+  uint64_t total = 0;
+  gko[0] = 0;
+  for (size_t a = 0; a < n_att; ++a) {
+    if (clen[a] > ATT_MAX_COMMITTEE || (uint64_t)coff[a] + clen[a] > n_shuffled || boff[a + 1] < boff[a])
+      return BLS381_EARG;
+    const size_t nbytes = boff[a + 1] - boff[a];
+    if (nbytes && (!agg || !cust)) return BLS381_EARG;
+    uint32_t n0 = 0, n1 = 0;
+    ok[a] = bitfield_ok(agg + boff[a], nbytes, clen[a]) && bitfield_ok(cust + boff[a], nbytes, clen[a]);
+    if (ok[a]) attesting_counts(agg + boff[a], cust + boff[a], nbytes, &n0, &n1);
+    desc[a] = att_desc{coff[a], clen[a], boff[a], (uint32_t)total, n0, n1};
+    total += (uint64_t)n0 + n1;
+    if (total > entries_cap || total > 0xFFFFFFFFull) return BLS381_EARG;
+    gko[2 * a + 1] = desc[a].out_off + n0;
+    gko[2 * a + 2] = (uint32_t)total;
+  }
+  return 0;
+}
+
+int bls381_attesting_entries_device(size_t n_att, const uint32_t* h_committee_off, const uint32_t* h_committee_len,
+                                    const uint32_t* h_bits_off, const uint8_t* h_aggregation_bits,
+                                    const uint8_t* h_custody_bits, const uint32_t* d_shuffled, size_t n_shuffled,
+                                    uint32_t* h_group_key_off, uint8_t* h_ok, uint32_t* d_entries, size_t entries_cap,
+                                    void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!h_group_key_off) return BLS381_EARG;
+    h_group_key_off[0] = 0;
+    if (n_att == 0) return 0;
+    if (!h_committee_off || !h_committee_len || !h_bits_off || !h_ok || !d_workspace || n_att > (size_t)INT32_MAX / 2 ||
+        (n_shuffled && !d_shuffled))
+      return BLS381_EARG;
+    const size_t bitfield_bytes = h_bits_off[n_att];
+    // the descriptors, and below the bitfields, in host blocks of the call's own: async copy sources
+    auto hold = std::make_shared<std::vector<att_desc>>(n_att);
+    TRY(att_plan(n_att, h_committee_off, h_committee_len, h_bits_off, h_aggregation_bits, h_custody_bits, n_shuffled,
+                 h_group_key_off, h_ok, entries_cap, hold->data()));
+    const size_t total = h_group_key_off[2 * n_att];
+    if (total == 0) return 0;
+    if (!d_entries) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_attesting_entries_workspace_size(n_att, bitfield_bytes));
+    const AttWs w = carve_att(b, n_att, bitfield_bytes);
+    auto bits = std::make_shared<std::vector<uint8_t>>(2 * bitfield_bytes);
+    std::memcpy(bits->data(), h_aggregation_bits, bitfield_bytes);
+    std::memcpy(bits->data() + bitfield_bytes, h_custody_bits, bitfield_bytes);
+    HIPC(hipMemcpyAsync(w.desc, hold->data(), n_att * sizeof(att_desc), hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(w.agg, bits->data(), bitfield_bytes, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(w.cust, bits->data() + bitfield_bytes, bitfield_bytes, hipMemcpyHostToDevice, s));
+    LAUNCH("attesting_entries", s, dim3((unsigned)n_att), dim3(ATT_BLOCK), k_attesting_entries, (const att_desc*)w.desc,
+           (const uint8_t*)w.agg, (const uint8_t*)w.cust, d_shuffled, d_entries);
+    TRY(keep_until_done(c, s, hold));
+    return keep_until_done(c, s, bits);
+  });
+}
+
+int bls381_attesting_entries(size_t n_att, const uint32_t* committee_off, const uint32_t* committee_len,
+                             const uint32_t* bits_off, const uint8_t* aggregation_bits, const uint8_t* custody_bits,
+                             const uint32_t* shuffled, size_t n_shuffled, uint32_t* group_key_off, uint8_t* ok,
+                             uint32_t* entries, size_t entries_cap) {
+  return guarded([&]() -> int {
+    if (!group_key_off) return BLS381_EARG;
+    group_key_off[0] = 0;
+    if (n_att == 0) return 0;
+    if (!bits_off || !committee_len || (n_shuffled && !shuffled)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_attesting_entries_workspace_size(n_att, bits_off[n_att]);
+    size_t most = 0;   // the two groups of an attestation are disjoint
+    for (size_t a = 0; a < n_att; ++a) most += committee_len[a];
+    const size_t ent_words = std::min(entries_cap, most);
+    uint32_t *d_sh, *d_ent;
+    uint8_t* d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_sh = b.take<uint32_t>(n_shuffled + 1);
+      d_ent = b.take<uint32_t>(ent_words + 1);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_sh, shuffled, 4 * n_shuffled));
+    TRY(bls381_attesting_entries_device(n_att, committee_off, committee_len, bits_off, aggregation_bits, custody_bits,
+                                        d_sh, n_shuffled, group_key_off, ok, entries ? d_ent : nullptr, entries_cap, d_ws,
+                                        hc.s));
+    TRY(hc.download(entries, d_ent, 4 * (size_t)group_key_off[2 * n_att]));
+    return hc.finish();
+  });
+}
+
 }  // extern "C"
 
 // ---- multi-GPU over RCCL: one process per GPU, a communicator

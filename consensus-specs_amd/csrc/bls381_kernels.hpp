@@ -12,6 +12,7 @@
 #include "bls381_pair.hpp"
 #include "bls381_quad.hpp"
 #include "bls381_ssz.hpp"
+#include "bls381_shuffle.hpp"
 
 namespace bls381 {
 
@@ -1949,6 +1950,81 @@ __global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_fp12_from_bytes(si
   fp2p_t* cs[6] = {&a.c0.c0, &a.c0.c1, &a.c0.c2, &a.c1.c0, &a.c1.c1, &a.c1.c2};
   for (int k = 0; k < 6; ++k) cs[k]->v = fp_to_mont(fp_plain_from_be48(in + 576 * i + 96 * k + 48 * p));
   soa_st12(f, n, i, a);
+}
+
+// ------------------------------ committees: shuffle and attesting entries (§7e) --
+// (the arithmetic and the layouts: bls381_shuffle.hpp)
+// pivots[r] of get_shuffled_index for a list of n, one lane per round
+__global__ void __launch_bounds__(KBLOCK) k_shuffle_pivots(uint32_t n, shuffle_seed seed, uint32_t rounds,
+                                                           uint32_t* __restrict__ pivots) {
+  const size_t r = item_index<1>();
+  if (r >= rounds) return;
+  pivots[r] = shuffle_pivot(seed, (uint32_t)r, n);
+}
+
+// table path, kernel A: the source digest of (round, block), one lane each; row r of the table is
+// blocks digests of 32 bytes
+__global__ void __launch_bounds__(KBLOCK) k_shuffle_table(shuffle_seed seed, uint32_t rounds, size_t blocks,
+                                                          uint32_t* __restrict__ table) {
+  const size_t t = item_index<1>();
+  if (t >= (size_t)rounds * blocks) return;
+  uint32_t w[8];
+  shuffle_source_words(w, seed, (uint32_t)(t / blocks), (uint32_t)(t % blocks));
+  uint4* o = (uint4*)(table + 8 * t);
+  o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// out[k] = shuffled(first + k), or indices[shuffled(first + k)], for k < count (first + count <= n)
+template <class Bit>
+__device__ __forceinline__ void dev_shuffle_out(uint32_t n, uint32_t rounds, const uint32_t* __restrict__ pivots,
+                                                const Bit& bit, uint32_t first, size_t count,
+                                                const uint32_t* __restrict__ indices, uint32_t* __restrict__ out) {
+  const size_t k = item_index<1>();
+  if (k >= count) return;
+  const uint32_t s = shuffle_walk(first + (uint32_t)k, n, rounds, pivots, bit);
+  out[k] = indices ? indices[s] : s;
+}
+
+// table path, kernel B: one lane per requested position, one table bit per round
+__global__ void __launch_bounds__(KBLOCK) k_shuffle_walk(uint32_t n, uint32_t rounds, const uint32_t* __restrict__ pivots,
+                                                         const uint32_t* __restrict__ table, size_t blocks,
+                                                         uint32_t first, size_t count,
+                                                         const uint32_t* __restrict__ indices,
+                                                         uint32_t* __restrict__ out) {
+  dev_shuffle_out(n, rounds, pivots, shuffle_table_bit<const uint32_t*>{table, 8 * blocks}, first, count, indices, out);
+}
+
+// direct path: one lane per requested position hashes its own source block in every round
+__global__ void __launch_bounds__(KBLOCK) k_shuffle_direct(uint32_t n, shuffle_seed seed, uint32_t rounds,
+                                                           const uint32_t* __restrict__ pivots, uint32_t first,
+                                                           size_t count, const uint32_t* __restrict__ indices,
+                                                           uint32_t* __restrict__ out) {
+  dev_shuffle_out(n, rounds, pivots, shuffle_direct_bit{seed}, first, count, indices, out);
+}
+
+struct wg_sync {
+  __device__ __forceinline__ void operator()() const { __syncthreads(); }
+};
+
+// convert_to_indexed's two sorted index sets, one workgroup per attestation (desc[blockIdx.x]):
+// group 2a then group 2a+1 at entries + out_off
+__global__ void __launch_bounds__(ATT_BLOCK) k_attesting_entries(const att_desc* __restrict__ desc,
+                                                                 const uint8_t* __restrict__ agg_bits,
+                                                                 const uint8_t* __restrict__ cust_bits,
+                                                                 const uint32_t* __restrict__ shuffled,
+                                                                 uint32_t* __restrict__ entries) {
+  __shared__ uint32_t buf[ATT_MAX_COMMITTEE];
+  __shared__ uint32_t cnt[ATT_MASK_WORDS];
+  const att_desc d = desc[blockIdx.x];
+  const uint32_t* committee = shuffled + d.committee_off;
+  const uint8_t *agg = agg_bits + d.bits_off, *cust = cust_bits + d.bits_off;
+  if (d.n0)
+    attesting_group(buf, cnt, threadIdx.x, ATT_BLOCK, wg_sync{}, committee, d.committee_len, agg, cust, 0, d.n0,
+                    entries + d.out_off);
+  if (d.n1)
+    attesting_group(buf, cnt, threadIdx.x, ATT_BLOCK, wg_sync{}, committee, d.committee_len, agg, cust, 1, d.n1,
+                    entries + d.out_off + d.n0);
 }
 
 }  // namespace bls381

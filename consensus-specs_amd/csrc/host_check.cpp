@@ -18,6 +18,7 @@
 #include "bls381_hash.hpp"
 #include "bls381_pairing.hpp"
 #include "bls381_plan.hpp"
+#include "bls381_shuffle.hpp"
 #include "bls381_ssz.hpp"
 
 using namespace bls381;
@@ -462,6 +463,75 @@ int hc_merkle_branch(const uint8_t* leaf32, const uint8_t* proof, uint32_t depth
   for (int w = 0; w < 8; ++w)
     for (int b = 0; b < 4; ++b) d |= (uint32_t)((uint8_t)(v[w] >> (24 - 8 * b)) ^ root32[4 * w + b]);
   return d == 0;
+}
+
+// get_shuffled_index (bls381_shuffle.hpp: the direct form, every position hashing its own source
+// block): the shuffled index, or UINT64_MAX for arguments the engine rejects
+uint64_t hc_shuffled_index(uint64_t index, uint64_t index_count, const uint8_t* seed32, uint32_t rounds) {
+  if (index_count > 0xFFFFFFFFull || index >= index_count || rounds > SHUFFLE_ROUNDS_MAX) return UINT64_MAX;
+  const shuffle_seed sd = shuffle_seed_from_bytes(seed32);
+  const uint32_t n = (uint32_t)index_count;
+  uint32_t pivots[SHUFFLE_ROUNDS_MAX + 1];
+  for (uint32_t r = 0; r < rounds; ++r) pivots[r] = shuffle_pivot(sd, r, n);
+  return shuffle_walk((uint32_t)index, n, rounds, pivots, shuffle_direct_bit{sd});
+}
+
+// Positions first .. first+count-1 of the shuffled list on `threads` host threads, through the
+// table form (table 1: shuffle_source_words per (round, block), then one bit per round) or the
+// direct form (table 0): the measurement base of tools/shuffle_bench.py and the table form's CPU
+// check.  0, or -1 for arguments the engine rejects.
+int hc_shuffle_list(uint64_t index_count, const uint8_t* seed32, uint32_t rounds, uint64_t first, uint64_t count,
+                    int table, int threads, uint32_t* out) {
+  if (index_count > 0xFFFFFFFFull || first > index_count || count > index_count - first ||
+      rounds > SHUFFLE_ROUNDS_MAX || threads < 1)
+    return -1;
+  if (count == 0) return 0;
+  const shuffle_seed sd = shuffle_seed_from_bytes(seed32);
+  const uint32_t n = (uint32_t)index_count;
+  const size_t blocks = shuffle_blocks(n);
+  std::vector<uint32_t> pivots(SHUFFLE_ROUNDS_MAX + 1), tab(table ? (size_t)rounds * blocks * 8 : 0);
+  for (uint32_t r = 0; r < rounds; ++r) pivots[r] = shuffle_pivot(sd, r, n);
+  auto run = [&](auto body) {
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; ++t) pool.emplace_back([=] { body((size_t)t); });
+    for (auto& th : pool) th.join();
+  };
+  if (table)
+    run([&](size_t t) {
+      for (size_t k = t; k < (size_t)rounds * blocks; k += (size_t)threads)
+        shuffle_source_words(&tab[8 * k], sd, (uint32_t)(k / blocks), (uint32_t)(k % blocks));
+    });
+  run([&](size_t t) {
+    for (uint64_t k = t; k < count; k += (uint64_t)threads) {
+      const uint32_t i = (uint32_t)(first + k);
+      out[k] = table ? shuffle_walk(i, n, rounds, pivots.data(), shuffle_table_bit<const uint32_t*>{tab.data(), 8 * blocks})
+                     : shuffle_walk(i, n, rounds, pivots.data(), shuffle_direct_bit{sd});
+    }
+  });
+  return 0;
+}
+
+// verify_bitfield (bls381_shuffle.hpp bitfield_ok): 1 / 0
+int hc_verify_bitfield(const uint8_t* bits, size_t nbytes, uint32_t committee_size) {
+  return bitfield_ok(bits, nbytes, committee_size);
+}
+
+// convert_to_indexed's two sets for one attestation (attesting_group, the code of
+// k_attesting_entries, run by one thread): out0 / out1 receive the sorted custody-bit-0 /
+// custody-bit-1 members (room for committee_len each), n_out their counts.  1, or 0 when a
+// bitfield fails verify_bitfield (both sets are then empty) or the committee exceeds 4,096.
+int hc_attesting_groups(const uint32_t* committee, uint32_t committee_len, const uint8_t* agg, const uint8_t* cust,
+                        size_t nbytes, uint32_t* out0, uint32_t* out1, uint32_t* n_out) {
+  n_out[0] = n_out[1] = 0;
+  if (committee_len > ATT_MAX_COMMITTEE || !bitfield_ok(agg, nbytes, committee_len) ||
+      !bitfield_ok(cust, nbytes, committee_len))
+    return 0;
+  attesting_counts(agg, cust, nbytes, &n_out[0], &n_out[1]);
+  std::vector<uint32_t> buf(ATT_MAX_COMMITTEE), cnt(ATT_MASK_WORDS);
+  const auto no_sync = [] {};
+  if (n_out[0]) attesting_group(buf.data(), cnt.data(), 0u, 1u, no_sync, committee, committee_len, agg, cust, 0, n_out[0], out0);
+  if (n_out[1]) attesting_group(buf.data(), cnt.data(), 0u, 1u, no_sync, committee, committee_len, agg, cust, 1, n_out[1], out1);
+  return 1;
 }
 
 #if defined(BLS_COUNT_OPS)

@@ -405,6 +405,58 @@ int bls381_registry_process_deposits_device(bls381_registry* reg, size_t n, cons
                                             int32_t* d_validator_index, int64_t* first_bad_proof, void* d_workspace,
                                             void* stream);
 
+/* ---- committees: the producer of the grouped verify's d_entries ---------- */
+/* get_shuffled_index (0_beacon-chain.md:860-882) for positions first .. first+count-1 of a list of
+ * index_count: out[k] = shuffled(first+k), or indices[shuffled(first+k)] when indices != NULL
+ * (compute_committee, :887-890: committee j of c is first = n*j/c, count = n*(j+1)/c - first;
+ * indices holds index_count entries).  rounds = SHUFFLE_ROUND_COUNT (90 mainnet, 10 minimal;
+ * 0..255, 0 = identity).  seed is host memory in both forms.
+ * Divergence: index_count is at most 2^32 - 1 where the spec allows 2^40 -- registry entries
+ * are 32-bit.  BLS381_EARG for a larger index_count, first + count > index_count, rounds > 255,
+ * or a NULL seed / out / workspace with count > 0; count == 0 is BLS381_OK and runs nothing.
+ * The call builds the table of all rounds * ceil(index_count / 256) source digests in the
+ * workspace (32 bytes each) and then reads one bit per round and position; only a window of at
+ * most ceil(index_count / 256) positions of a list of more than 2^24 - 256 hashes its own source
+ * blocks instead (workspace: the pivots), where the table's build outweighs the window's
+ * rounds hashes in sequence.  The device
+ * form is queued on `stream`, not synchronised; d_workspace holds
+ * bls381_shuffle_workspace_size(index_count, count, rounds) bytes (0 for arguments the call
+ * rejects). */
+size_t bls381_shuffle_workspace_size(uint64_t index_count, uint64_t count, uint32_t rounds);
+int bls381_shuffle(uint64_t index_count, const uint8_t seed[32], uint32_t rounds, uint64_t first, uint64_t count,
+                   const uint32_t* indices, uint32_t* out);
+int bls381_shuffle_device(uint64_t index_count, const uint8_t seed[32], uint32_t rounds, uint64_t first,
+                          uint64_t count, const uint32_t* d_indices, uint32_t* d_out, void* d_workspace,
+                          void* stream);
+
+/* convert_to_indexed's index sets (0_beacon-chain.md:905-917, :988-1001) for n_att attestations
+ * over one shuffled list, as two groups per attestation in the order the grouped verify takes
+ * them: group 2a = custody bit 0 (aggregation bit set and custody bit clear), group 2a+1 =
+ * custody bit 1 (custody bit set, whatever the aggregation bit: get_attesting_indices(...,
+ * custody_bitfield)), each sorted ascending.  Attestation a's committee is
+ * shuffled[committee_off[a] .. + committee_len[a]) (a compute_committee result; at most 4,096 =
+ * MAX_INDICES_PER_ATTESTATION members) and its two bitfields are bytes [bits_off[a],
+ * bits_off[a+1]) of aggregation_bits and of custody_bits (bits_off: n_att + 1 entries).
+ * The host half runs verify_bitfield (:970-982) on both bitfields -- ok[a] = 0 and two empty
+ * groups when either fails -- and the popcounts: group_key_off (2 n_att + 1 entries, a host
+ * output) is the h_group_key_off of bls381_registry_verify_multiple_grouped_device, d_entries its
+ * d_entries, with h_call_group_off = [0, 2, 4, ...].  Entries past group_key_off[2 n_att] are not
+ * written.  BLS381_EARG: a committee longer than 4,096 or outside n_shuffled, entries_cap (in
+ * entries) below the member total, descending bits_off, or a NULL argument that is needed.  The
+ * device form copies the bitfields into the workspace
+ * (bls381_attesting_entries_workspace_size(n_att, bits_off[n_att])) and is queued on `stream`,
+ * not synchronised; the host outputs are complete when it returns. */
+size_t bls381_attesting_entries_workspace_size(size_t n_att, size_t bitfield_bytes);
+int bls381_attesting_entries(size_t n_att, const uint32_t* committee_off, const uint32_t* committee_len,
+                             const uint32_t* bits_off, const uint8_t* aggregation_bits, const uint8_t* custody_bits,
+                             const uint32_t* shuffled, size_t n_shuffled, uint32_t* group_key_off, uint8_t* ok,
+                             uint32_t* entries, size_t entries_cap);
+int bls381_attesting_entries_device(size_t n_att, const uint32_t* h_committee_off, const uint32_t* h_committee_len,
+                                    const uint32_t* h_bits_off, const uint8_t* h_aggregation_bits,
+                                    const uint8_t* h_custody_bits, const uint32_t* d_shuffled, size_t n_shuffled,
+                                    uint32_t* h_group_key_off, uint8_t* h_ok, uint32_t* d_entries, size_t entries_cap,
+                                    void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
