@@ -238,7 +238,7 @@ struct VerifyIn {
 
 unsigned grid_for(size_t n, int block = KBLOCK) { return (unsigned)((n + block - 1) / block); }
 
-// The clock-based wave balance (bls381_pair.hpp, BLS_WAVE_BALANCE=2) runs in a launch with no LDS
+// The clock-based wave balance (bls381_pair.hpp, wave_balance) runs in a launch with no LDS
 // allocation; launch() gives every other launch 256 B of dynamic LDS (no kernel reads it) as the
 // switch, which the device tests with one s_getreg.  Balanced: launches that put two waves on every
 // SIMD, all resident from the start (CUs x 4 SIMDs x 64 < lanes <= CUs x 4 x 2 x 64) -- in a

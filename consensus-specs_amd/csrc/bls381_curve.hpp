@@ -140,7 +140,9 @@ BLS_DEV_INLINE bool jac_to_aff(aff_t<F>& out, const jac_t<F>& p) {
 
 // Scalar multiplications are one (non-inlined) function each, with the point
 // formulas inlined into the loop, so the running point stays in registers.
-// [k] a for a 64-bit scalar, affine base, left-to-right (the body, for callers that inline it)
+// [k] a for a 64-bit scalar, affine base, left-to-right.  The body is a function of its own under
+// the non-inlined one (here and for the Jacobian base below): written into jac_mul_u64 directly it
+// compiles to other instructions, so it stays until that is worth a measurement.
 template <class F>
 BLS_DEV_INLINE jac_t<F> jac_mul_u64_body(const aff_t<F>& a, uint64_t k) {
   jac_t<F> r = jac_from_aff(a);

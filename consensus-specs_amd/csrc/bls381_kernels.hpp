@@ -97,6 +97,17 @@ __device__ __forceinline__ aff_t<fp2p_t> soa_ld_g2(const uint32_t* p, size_t n, 
 __device__ __forceinline__ void soa_st_g2(uint32_t* p, size_t n, size_t i, const aff_t<fp2p_t>& a) {
   soa_st2p(p, n, i, 0, a.x); soa_st2p(p, n, i, 1, a.y);
 }
+// the G1 side of a Miller pair: item i of the n points p, or -[c] g1 (the constant G1_VGEN, the
+// signature's partner: bls381_hash.hpp g2_mul_bp) for p == nullptr
+__device__ __forceinline__ aff_t<fp_t> soa_ld_g1_or_vgen(const uint32_t* p, size_t n, size_t i) {
+  aff_t<fp_t> P;
+  if (p) {
+    P = soa_ld_g1(p, n, i);
+  } else {
+    P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
+  }
+  return P;
+}
 using fp12p_t = fp12_g<fp2p_t>;
 __device__ __forceinline__ fp12p_t soa_ld12(const uint32_t* p, size_t n, size_t i) {
   fp12p_t f;
@@ -287,16 +298,13 @@ __global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_decode_g2_1(size_t
 // per item, where the pair form computes them on both lanes), then the cofactor map BP and
 // the affine conversion on lane pairs (k_hash_bp, in place over the candidate points).
 //
-// BLS_HASH_COMPACT=1: the try-and-increment search runs over the whole wave as a pool.
+// The try-and-increment search runs over the whole wave as a pool.
 // A lane-per-item loop runs until the wave's slowest item has found its square (~7 rounds
 // for 64 items at success probability 1/2, against a mean of 2).  Here, each round,
 // the wave's unresolved items share all 64 lanes: with m items left, item t (the r-th
 // unresolved) takes the lanes j = r, r + m, r + 2m, ... and tests its offsets k_t, k_t + 1,
 // ... one per lane; its square is the lowest successful offset (the spec's candidate
 // order), else k_t advances past all of them.  ~3 rounds per wave.
-#ifndef BLS_HASH_COMPACT
-#define BLS_HASH_COMPACT 1
-#endif
 
 // the r-th set bit (r < popcount(m)) of a 64-bit mask
 __device__ __forceinline__ uint32_t nth_set_bit64(uint64_t m, uint32_t r) {
@@ -318,7 +326,6 @@ __device__ __forceinline__ uint32_t lane_shfl(uint32_t v, uint32_t src) {
 __device__ __forceinline__ void dev_hash_cand_1(size_t i, size_t n, const uint8_t* __restrict__ msgs, uint32_t mlen,
                                                 const uint8_t* __restrict__ doms, int dom_stride,
                                                 uint32_t* __restrict__ out) {
-#if BLS_HASH_COMPACT
   // every lane of the wave takes part in the pooled search: no early return before it
   const bool valid = i < n;
   fp2_t x;
@@ -376,14 +383,6 @@ __device__ __forceinline__ void dev_hash_cand_1(size_t i, size_t n, const uint8_
   c.x = x;
   c.y = g2_select_root(y);
   soa_st_g2_1(out, n, i, c);
-#else
-  if (i >= n) return;
-  uint8_t dom[8];
-  ld_bytes(dom, doms + (size_t)dom_stride * i, 8);
-  aff_t<fp2_t> c;
-  hash_to_g2_candidate(c, msgs + (size_t)mlen * i, mlen, dom);
-  soa_st_g2_1(out, n, i, c);
-#endif
 }
 __global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_hash_cand_1(size_t n, const uint8_t* __restrict__ msgs,
                                                        uint32_t mlen, const uint8_t* __restrict__ doms,
@@ -485,19 +484,12 @@ __device__ __forceinline__ void quad_line_pair(const fp2p_t& x0, const fp2p_t& x
   o2 = p1;
 }
 
-// BLS_ML_L_NT=1 (default): the line products are stored non-temporally -- they stream through HBM
-// to k_ml_accum, and the lines kernel's own scratch keeps the caches.  r04e, one box, two runs each:
+// The line products are stored non-temporally -- they stream through HBM to k_ml_accum, and the
+// lines kernel's own scratch keeps the caches.  Against plain stores (r04e, one box, two runs each):
 // k_ml_lines 6.69 / 6.70 -> 6.59 / 6.61 ms, k_ml_accum 7.29 / 7.30 -> 7.17 / 7.25 ms.
-#ifndef BLS_ML_L_NT
-#define BLS_ML_L_NT 1
-#endif
 __device__ __forceinline__ void soa_st_L(uint32_t* __restrict__ p, size_t n, size_t i, int c, const fp_t& a) {
-#if BLS_ML_L_NT
 #pragma unroll
   for (int k = 0; k < FP_LIMBS; ++k) __builtin_nontemporal_store(a.w[k], &((g_u32*)p)[(size_t)(c * FP_LIMBS + k) * n + i]);
-#else
-  soa_st(p, n, i, c, a);
-#endif
 }
 __device__ __forceinline__ void ml_store_L(uint32_t* __restrict__ L, size_t cnt, size_t i, int j, bool hi,
                                            const fp2p_t& o0, const fp2p_t& o1, const fp2p_t& o2) {
@@ -508,36 +500,13 @@ __device__ __forceinline__ void ml_store_L(uint32_t* __restrict__ L, size_t cnt,
   if (!hi) soa_st_L(L, 2 * cnt, col, c + 2, o2.v);
 }
 
-// the 68 steps of one half's running point, with the quad's line products written to L
-__device__ __noinline__ g2_proj<fp2p_t> ml_lines_run(const aff_t<fp2p_t> Q, const g1_line_pre pre, bool active,
-                                                    uint32_t* __restrict__ L, size_t cnt, size_t li) {
-  const bool hi = qd_hi();
-  const fp2p_t one = e2_one<fp2p_t>(), zero = e2_zero<fp2p_t>();
-  g2_proj<fp2p_t> T;
-  T.x = Q.x; T.y = Q.y; T.z = one;
-  int j = 0;
-  for (int b = 62; b >= 0; --b) {
-    fp2p_t c0, c1, c2, o0, o1, o2;
-    line_dbl(T, pre, c0, c1, c2);
-    quad_line_pair(qd_sel(active, c0, one), qd_sel(active, c1, zero), qd_sel(active, c2, zero), o0, o1, o2);
-    ml_store_L(L, cnt, li, j++, hi, o0, o1, o2);
-    if ((BLS_X_ABS >> b) & 1) {
-      line_add(T, Q, pre, c0, c1, c2);
-      quad_line_pair(qd_sel(active, c0, one), qd_sel(active, c1, zero), qd_sel(active, c2, zero), o0, o1, o2);
-      ml_store_L(L, cnt, li, j++, hi, o0, o1, o2);
-    }
-  }
-  return T;
-}
-
-// BLS_ML_LINES_LDS=1: the doubling steps' line constants (-3 xp, 2 yp: 28 words per lane) live in
+// The 68 steps of one half's running point, with the quad's line products written to L
+// (ml_lines_run_lds).  The doubling steps' line constants (-3 xp, 2 yp: 28 words per lane) live in
 // LDS (14 KB per workgroup of 128 lanes), and Q and the addition steps' constants (-xp, yp) are
-// re-read from their SoA rows at each of the five addition steps.  Without it the loop keeps
-// all of them in the kernel's scratch frame (its live set is over the VGPR budget) and re-reads
-// them through flat loads at every step: most of k_ml_lines' HBM traffic beyond L itself.
-#ifndef BLS_ML_LINES_LDS
-#define BLS_ML_LINES_LDS 1
-#endif
+// re-read from their SoA rows at each of the five addition steps.  The older form, with all of them
+// as arguments, kept them in the kernel's scratch frame (its live set is over the VGPR budget) and
+// re-read them through flat loads at every step: most of k_ml_lines' HBM traffic beyond L itself;
+// k_ml_lines 6.51-6.58 -> 6.02-6.05 ms (HISTORY.md, "ml_lines_run_lds").
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 // where a half's pair lives: Q (pair SoA of nq2 lanes, lane lp), P (G1 SoA of np items, item
 // ip) or, with p == nullptr, -[c] g1 (the constant G1_VGEN)
@@ -553,15 +522,7 @@ __device__ __forceinline__ aff_t<fp2p_t> ml_src_q(const ml_src& s) {
   Q.y = pr_make(soa_ld(s.q, s.nq2, s.lp, 1));
   return Q;
 }
-__device__ __forceinline__ aff_t<fp_t> ml_src_p(const ml_src& s) {
-  aff_t<fp_t> P;
-  if (s.p) {
-    P = soa_ld_g1(s.p, s.np, s.ip);
-  } else {
-    P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
-  }
-  return P;
-}
+__device__ __forceinline__ aff_t<fp_t> ml_src_p(const ml_src& s) { return soa_ld_g1_or_vgen(s.p, s.np, s.ip); }
 // this lane's column of the LDS line constants: word k of -3 xp at col[k KBLOCK], of 2 yp at
 // col[(14 + k) KBLOCK] (lane-major: conflict-free)
 struct g1_dbl_lds { const lds_u32* col; };
@@ -589,7 +550,7 @@ __device__ __forceinline__ void ml_lds_put(lds_u32* col, const g1_line_pre& pre)
 // caller's frame after every store)
 // (the final running point is returned by value: no pointer into the caller's frame)
 // bal: the launch is one round of two-wave slots (the host's choice, bls381_capi.hip): the
-// steps alternate the priority by the clock (BLS_WAVE_BALANCE=2), else by step parity
+// steps alternate the priority by the clock (bls381_pair.hpp), else by step parity
 __device__ __noinline__ g2_proj<fp2p_t> ml_lines_run_lds(const ml_src src, const lds_u32* col, bool active,
                                                         uint32_t* __restrict__ L, size_t cnt, size_t li,
                                                         int bal) {
@@ -603,13 +564,8 @@ __device__ __noinline__ g2_proj<fp2p_t> ml_lines_run_lds(const ml_src src, const
   const g1_dbl_lds dp{col};
   int j = 0;
   for (int b = 62; b >= 0; --b) {
-#if BLS_WAVE_BALANCE == 2
     if (bal) wave_prio(balance_clock());
     else wave_balance_lds((unsigned)b);
-#else
-    (void)bal;
-    wave_balance_lds((unsigned)b);
-#endif
     fp2p_t c0, c1, c2, o0, o1, o2;
     line_dbl(T, dp, c0, c1, c2);
     quad_line_pair(qd_sel(active, c0, one), qd_sel(active, c1, zero), qd_sel(active, c2, zero), o0, o1, o2);
@@ -655,26 +611,12 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_ml_lines(size_t
   const bool use_pk = hi ? pk_ok : !sig_ok;
   const uint32_t* qsrc = use_pk ? h_aff : sig_aff;
   g2_proj<fp2p_t> T;
-#if BLS_ML_LINES_LDS
   __shared__ uint32_t lds_pre[ML_LDS_WORDS];
   lds_u32* col = (lds_u32*)lds_pre + threadIdx.x;
   const ml_src src{qsrc, 2 * n, lp, use_pk ? pk_aff : nullptr, n, i};
   ml_lds_put(col, g1_prepare(ml_src_p(src)));   // each lane writes and reads only its own column
   T = ml_lines_run_lds(src, col, active, L, cnt, li, bal);
   const aff_t<fp2p_t> Q = ml_src_q(src);
-#else
-  aff_t<fp2p_t> Q;
-  Q.x = pr_make(soa_ld(qsrc, 2 * n, lp, 0));
-  Q.y = pr_make(soa_ld(qsrc, 2 * n, lp, 1));
-  aff_t<fp_t> P;
-  if (use_pk) {
-    P = soa_ld_g1(pk_aff, n, i);
-  } else {
-    P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
-  }
-  const g1_line_pre pre = g1_prepare(P);
-  T = ml_lines_run(Q, pre, active, L, cnt, li);
-#endif
   // py_ecc's zero pairing value for a degenerate loop; the strict policy's G2 test of the
   // signature on the lo half's final point (psi(sig) == -[|x|] sig)
   bool bad = active && fp2_is_zero(T.z);
@@ -696,74 +638,13 @@ __device__ __forceinline__ fp12p_t ml_load_L(const uint32_t* __restrict__ L, siz
   return r;
 }
 
-// BLS_ML_ACCUM_LDS=1: k_ml_accum stages each step's L (5 Fp per lane) in LDS -- each lane its
-// own column, 35 KB per workgroup -- and reads every coefficient at its use, instead of holding
-// all five (70 VGPRs) beside f through the step's 29 Fp2 products.
-#ifndef BLS_ML_ACCUM_LDS
-#define BLS_ML_ACCUM_LDS 0
-#endif
-constexpr int ML_ACC_LDS_WORDS = ML_LC * FP_LIMBS * KBLOCK;
-// volatile: within one lane the compiler would otherwise forward the staged values from the
-// registers that stored them (no other lane reads the column) and drop LDS altogether
-__device__ __forceinline__ fp2p_t ml_lds_c(const lds_u32* col, int c) {
-  const volatile lds_u32* v = col;
-  fp_t r;
-#pragma unroll
-  for (int k = 0; k < FP_LIMBS; ++k) r.w[k] = v[(c * FP_LIMBS + k) * KBLOCK];
-  return pr_make(r);
-}
-// step j's L from HBM into this lane's LDS column, one coefficient at a time
-__device__ __forceinline__ void ml_stage_L(lds_u32* col, const uint32_t* __restrict__ L, size_t cnt, size_t i, int j) {
-  const size_t lane = 2 * i + (pr_odd() ? 1 : 0);
-#pragma unroll
-  for (int c = 0; c < ML_LC; ++c) {
-    const fp_t v = soa_ld(L, 2 * cnt, lane, j * ML_LC + c);
-    volatile lds_u32* d = col;
-#pragma unroll
-    for (int k = 0; k < FP_LIMBS; ++k) d[(c * FP_LIMBS + k) * KBLOCK] = v.w[k];
-  }
-}
-// fp12_mul_by_line_pair_inl (bls381_pairing.hpp) with L read from LDS at each use:
-// L = (L00 + L01 v + L02 v^2) + (L11 v + L12 v^2) w, coefficients 0..4 of the column
-__device__ __forceinline__ fp12p_t fp12_mul_by_line_pair_lds(const fp12p_t& f, const lds_u32* col) {
-  const fp6p_t& a = f.c0;
-  const fp6p_t& b = f.c1;
-  fp6p_t aP;
-  {
-    const fp2p_t t0 = fp2_mul(a.c0, ml_lds_c(col, 0));
-    const fp2p_t t1 = fp2_mul(a.c1, ml_lds_c(col, 1));
-    const fp2p_t t2 = fp2_mul(a.c2, ml_lds_c(col, 2));
-    aP.c0 = fp2_add_xi_sub2(t0, fp2_mul(fp2_add_lazy(a.c1, a.c2),
-                                        fp2_add_lazy(ml_lds_c(col, 1), ml_lds_c(col, 2))), t1, t2);
-    aP.c1 = fp2_sub2_add_xi(fp2_mul(fp2_add_lazy(a.c0, a.c1),
-                                    fp2_add_lazy(ml_lds_c(col, 0), ml_lds_c(col, 1))), t0, t1, t2);
-    aP.c2 = fp2_sub2_add(fp2_mul(fp2_add_lazy(a.c0, a.c2),
-                                 fp2_add_lazy(ml_lds_c(col, 0), ml_lds_c(col, 2))), t0, t2, t1);
-  }
-  fp6p_t bQ;
-  {
-    const fp2p_t t1 = fp2_mul(b.c1, ml_lds_c(col, 3));
-    const fp2p_t t2 = fp2_mul(b.c2, ml_lds_c(col, 4));
-    bQ.c0 = fp2_add_xi_sub2(e2_zero<fp2p_t>(),
-                            fp2_mul(fp2_add_lazy(b.c1, b.c2), fp2_add_lazy(ml_lds_c(col, 3), ml_lds_c(col, 4))), t1, t2);
-    bQ.c1 = fp2_add_mul_xi(fp2_mul(b.c0, ml_lds_c(col, 3)), t2);
-    bQ.c2 = fp2_add(fp2_mul(b.c0, ml_lds_c(col, 4)), t1);
-  }
-  fp6p_t pq;
-  pq.c0 = ml_lds_c(col, 0);
-  pq.c1 = fp2_add(ml_lds_c(col, 1), ml_lds_c(col, 3));
-  pq.c2 = fp2_add(ml_lds_c(col, 2), ml_lds_c(col, 4));
-  const fp6p_t m = fp6_mul_inl(fp6_add(a, b), pq);
-  fp12p_t r;
-  r.c0 = fp6_add_mul_by_v(aP, bQ);
-  r.c1 = fp6_sub2(m, aP, bQ);
-  return r;
-}
-
 // f = conj(prod_j L_j^(2^(later doublings))) for items i0 .. i0 + cnt - 1; writes f (SoA over n
 // items, the layout k_final_exp_verdict reads) and the item status.  grp > 0 (randomized
 // batches): item i's value goes to slot (i / grp) (grp + 1) + i % grp of n slots, so every
 // group of grp values leaves a slot free after it (the signature-sum value of a sub-batch).
+// Each step's L (5 Fp per lane, 70 VGPRs) is held in registers beside f through the step's 29 Fp2
+// products; staging it in LDS and reading each coefficient at its use (35 KB per workgroup)
+// measured neutral, 7.08-7.13 against 7.09-7.14 ms (HISTORY.md).
 __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_ml_accum(size_t n, size_t i0, size_t cnt,
                                                     const uint32_t* __restrict__ L,
                                                     const uint8_t* __restrict__ st_in,
@@ -779,24 +660,6 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_ml_accum(size_t
   if (s == ML_ST_ONE) {
     f = fp12_one<fp2p_t>();
   } else {
-#if BLS_ML_ACCUM_LDS
-    __shared__ uint32_t lds_L[ML_ACC_LDS_WORDS];
-    lds_u32* col = (lds_u32*)lds_L + threadIdx.x;   // each lane writes and reads only its own column
-    f = ml_load_L(L, cnt, li, 0);
-    int j = 1;
-    if ((BLS_X_ABS >> 62) & 1) {
-      ml_stage_L(col, L, cnt, li, j++);
-      f = fp12_mul_by_line_pair_lds(f, col);
-    }
-    for (int b = 61; b >= 0; --b) {
-      ml_stage_L(col, L, cnt, li, j++);
-      f = fp12_mul_by_line_pair_lds(fp12_sqr_inl(f), col);
-      if ((BLS_X_ABS >> b) & 1) {
-        ml_stage_L(col, L, cnt, li, j++);
-        f = fp12_mul_by_line_pair_lds(f, col);
-      }
-    }
-#else
     f = ml_load_L(L, cnt, li, 0);
     int j = 1;
     if ((BLS_X_ABS >> 62) & 1) f = fp12_mul_by_line_pair_inl(f, ml_load_L(L, cnt, li, j++));
@@ -805,7 +668,6 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_ml_accum(size_t
       f = fp12_mul_by_line_pair_inl(fp12_sqr_inl(f), ml_load_L(L, cnt, li, j++));
       if ((BLS_X_ABS >> b) & 1) f = fp12_mul_by_line_pair_inl(f, ml_load_L(L, cnt, li, j++));
     }
-#endif
     f = fp12_conj(f);
   }
   soa_st12(f_out, n, i, f);
@@ -917,16 +779,8 @@ __device__ __forceinline__ void miller_pair_store(bool active, const uint32_t* _
   fq12_t f;
   bool degen = false;
   if (active) {
-    const int p = pr_odd() ? 1 : 0;
-    aff_t<fp2p_t> Q;
-    Q.x = pr_make(soa_ld(q_aff, 2 * cnt, 2 * idx + p, 0));
-    Q.y = pr_make(soa_ld(q_aff, 2 * cnt, 2 * idx + p, 1));
-    aff_t<fp_t> P;
-    if (p_aff) {
-      P = soa_ld_g1(p_aff, cnt, idx);
-    } else {
-      P.x = G1_VGEN_X_M; P.y = G1_VGEN_NEGY_M;
-    }
+    const aff_t<fp2p_t> Q = soa_ld_g2(q_aff, cnt, idx);
+    const aff_t<fp_t> P = soa_ld_g1_or_vgen(p_aff, cnt, idx);
     f = miller_loop_lg<G>(Q, g1_prepare(P), degen);
   } else {
     f = fq12_one();
@@ -1318,19 +1172,11 @@ __global__ void __launch_bounds__(KBLOCK, BLS_ML_WAVES_PER_EU) k_rb_ml_lines(siz
   const size_t i = (hi ? b_ok : !a_ok) ? ib : ia;
   const size_t lp = 2 * i + (pr_odd() ? 1 : 0);
   g2_proj<fp2p_t> T;
-#if BLS_ML_LINES_LDS
   __shared__ uint32_t lds_pre[ML_LDS_WORDS];
   lds_u32* col = (lds_u32*)lds_pre + threadIdx.x;
   const ml_src src{h_aff, 2 * n, lp, r1_aff, n, i};
   ml_lds_put(col, g1_prepare(ml_src_p(src)));
   T = ml_lines_run_lds(src, col, active, L, cnt, lq, 0);
-#else
-  aff_t<fp2p_t> Q;
-  Q.x = pr_make(soa_ld(h_aff, 2 * n, lp, 0));
-  Q.y = pr_make(soa_ld(h_aff, 2 * n, lp, 1));
-  const g1_line_pre pre = g1_prepare(soa_ld_g1(r1_aff, n, i));
-  T = ml_lines_run(Q, pre, active, L, cnt, lq);
-#endif
   bool bad = active && fp2_is_zero(T.z);
   bad = !qd_all(!bad);
   if (lead) st_out[lq] = bad ? ST_BAD : ST_OK;

@@ -34,13 +34,6 @@ BLS_INLINE void wz_init(wide_t& T) {
   for (int j = 0; j < 14; ++j) T.c[13 + j] = (int64_t)Q_LIMBS[j] << WIDE_OFF_SHIFT;
 }
 
-// BLS_LAZY_CSQR_V2 (default 1; 0 = the round-4 form, measurement knob): the compressed
-// squaring's column offsets ride on each column's first product (wmac_init) and u = b0 -+ b1
-// of lz_sqr_xisqr is squared unreduced (signed limbs)
-#ifndef BLS_LAZY_CSQR_V2
-#define BLS_LAZY_CSQR_V2 1
-#endif
-
 // T += x y  (signed limbs)
 BLS_INLINE void wmac(wide_t& T, const lv_t& x, const lv_t& y) {
   BLS_COUNT_MACS(196);
@@ -51,13 +44,10 @@ BLS_INLINE void wmac(wide_t& T, const lv_t& x, const lv_t& y) {
 }
 
 // T = x y + the offset of wz_init: each column's first product takes the column's initial
-// value as its addend (one v_mad with a scalar operand) instead of a separate move
+// value as its addend (one v_mad with a scalar operand) instead of a separate move.  With
+// lz_sqr_xisqr's unreduced u this replaced the round-4 form (wz_init then wmac, u reduced mod 2q
+// first): fe_phases 6.71 against 6.74 M cycles (HISTORY.md)
 BLS_INLINE void wmac_init(wide_t& T, const lv_t& x, const lv_t& y) {
-#if !BLS_LAZY_CSQR_V2
-  wz_init(T);
-  wmac(T, x, y);
-  return;
-#endif
   BLS_COUNT_MACS(196);
 #pragma unroll
   for (int i = 0; i < 14; ++i)
@@ -194,14 +184,6 @@ BLS_INLINE fp_t lz_sqr_xisqr(bool p, const fp_t& a0, const fp_t& a1, const fp_t&
     u[k] = p ? c + d : c - d;
     v[k] = d;
   }
-#if !BLS_LAZY_CSQR_V2
-  {
-    uint32_t s[14];
-#pragma unroll
-    for (int k = 0; k < 14; ++k) s[k] = b0.w[k] + (p ? b1.w[k] : Q2B_LIMBS[k] - b1.w[k]);
-    lv_from(u, fp_reduce_lc<2>(s));
-  }
-#endif
   wide_t T;
   wmac_init(T, x1, y1);
   wsqr_k(T, u, 1);

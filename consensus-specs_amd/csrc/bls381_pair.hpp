@@ -25,23 +25,19 @@
 // issue slots and finishes first, and the younger runs the rest of its work alone at a lone wave's
 // issue rate: in k_final_exp_verdict's shape the older wave of every SIMD ends at 6.2 ms, the
 // younger at 9.4 (tools/fe_phases.hip, profiles/fe_balance_r06.txt).
-//   BLS_WAVE_BALANCE=2 (default, round 6): in a launch that puts two waves on every SIMD, all resident
-//     from the start (one round of two-wave slots), the priority alternates with the real-time clock
-//     (windows of 2^BLS_BALANCE_SHIFT ticks of s_memrealtime's 100 MHz), so both waves hold it for
-//     equal times: 8.5 / 9.0 ms.  It is updated before every lane-pair Fp2 product call and at the
-//     loops' steps.  The host picks those launches (bls381_capi.hip, balance_lds) and marks every
-//     other one with an LDS allocation, which the device reads with one s_getreg; those keep the
-//     step-parity form of 1 at the loops' steps.  Same box, alternating (profiles/ab_r06p_balance.txt):
-//     C2 +1.0 to +2.3 %; k_final_exp_verdict 8.79-8.94 -> 8.45-8.51 ms, k_ml_accum 6.88-6.96 ->
-//     6.61-6.64, k_hash_bp 3.27-3.31 -> 3.19; k_ml_lines 6.03-6.08 -> 6.32-6.38 (its loop function's
-//     allocation around the calls came out with more spill traffic).  k_ml_lines has static LDS, so
-//     the switch is off in it; its launches are one round each and pass the choice as an argument
-//     (bls381_kernels.hpp, ml_lines_run_lds).
-//   BLS_WAVE_BALANCE=1 (round 4): alternate by step parity at the loops' steps only.  It does not
-//     balance: a wave one step ahead has the same priority as the other, which the older wins.
-#ifndef BLS_WAVE_BALANCE
-#define BLS_WAVE_BALANCE 2
-#endif
+// In a launch that puts two waves on every SIMD, all resident from the start (one round of two-wave
+// slots), the priority alternates with the real-time clock (windows of 2^BLS_BALANCE_SHIFT ticks of
+// s_memrealtime's 100 MHz), so both waves hold it for equal times: 8.5 / 9.0 ms.  It is updated
+// before every lane-pair Fp2 product call and at the loops' steps.  The host picks those launches
+// (bls381_capi.hip, balance_lds) and marks every other one with an LDS allocation, which the device
+// reads with one s_getreg; those alternate by step parity at the loops' steps.  Same box, alternating
+// (profiles/ab_r06p_balance.txt): C2 +1.0 to +2.3 %; k_final_exp_verdict 8.79-8.94 -> 8.45-8.51 ms,
+// k_ml_accum 6.88-6.96 -> 6.61-6.64, k_hash_bp 3.27-3.31 -> 3.19; k_ml_lines 6.03-6.08 -> 6.32-6.38
+// (its loop function's allocation around the calls came out with more spill traffic).  k_ml_lines
+// has static LDS, so the clock form is off in it; its launches are one round each and pass the choice
+// as an argument (bls381_kernels.hpp, ml_lines_run_lds).
+// Step parity everywhere (round 4) does not balance: a wave one step ahead has the same priority as
+// the other, which the older wins; no priority at all is the 6.2 / 9.4 ms above (HISTORY.md).
 // 2^16 ticks = 655 us: against 2^14 (164 us), same box, C2 -0.2 to +2.3 %, k_ml_lines 6.21-6.32 ->
 // 6.05-6.16 ms, FE 8.38-8.42 -> 8.27-8.33 (profiles/ab_r06st_balance_window.txt; 2^13 and 2^15 too)
 #ifndef BLS_BALANCE_SHIFT
@@ -64,31 +60,19 @@ __device__ __forceinline__ unsigned balance_clock() {
 }
 // at a loop step
 __device__ __forceinline__ void wave_balance(unsigned step) {
-#if BLS_WAVE_BALANCE == 2
   if (!wave_has_lds()) wave_prio(balance_clock());
   else wave_prio(step);
-#elif BLS_WAVE_BALANCE == 1
-  wave_prio(step);
-#else
-  (void)step;
-#endif
 }
 // at a loop step of a kernel that always has an LDS allocation (the line loop): the step-parity form
 __device__ __forceinline__ void wave_balance_lds(unsigned step) {
-#if BLS_WAVE_BALANCE
   wave_prio(step);
-#else
-  (void)step;
-#endif
 }
 // at an Fp2 product call
 __device__ __forceinline__ void wave_balance_call() {
-#if BLS_WAVE_BALANCE == 2
   if (!wave_has_lds()) wave_prio(balance_clock());
-#endif
 }
 }  // namespace bls381
-#if BLS_WAVE_BALANCE && !defined(BLS_FE_STEP)
+#ifndef BLS_FE_STEP
 #define BLS_FE_STEP(j) ::bls381::wave_balance((unsigned)(j))
 #endif
 #include "bls381_hash.hpp"
@@ -325,9 +309,6 @@ __device__ __forceinline__ cyc_bc<fp2p_t> cyc_csqr_lazy(const cyc_bc<fp2p_t>& g)
 // the other's row by DPP.  Lane-relative: X = this lane's row, Y = the partner's, so lane 0 has
 // (X, Y, U, V) = (a, b, u, v) and lane 1 (b, a, v, u), and both apply the same code with
 // (cX, cY) = (f0, g0) on lane 0 and (g1, f1) on lane 1.  Half of fp_inv's full-width work per lane.
-#ifndef BLS_INV_PAIR
-#define BLS_INV_PAIR 1
-#endif
 __device__ inline fp_t fp_inv_pair(const fp_t am) {
   const bool odd = pr_odd();
   uint32_t w[12];
@@ -425,11 +406,7 @@ __device__ inline fp_t fp_inv_pair(const fp_t am) {
 // 1/a = conj(a) / (a0^2 + a1^2); the norm (the same on both lanes) is inverted by the pair
 __device__ inline fp2p_t fp2_inv(const fp2p_t a) {
   const fp_t t = fp_sqr(a.v);
-#if BLS_INV_PAIR
   const fp_t ni = fp_inv_pair(fp_add(t, pr_dpp<DPP_SWAP>(t)));
-#else
-  const fp_t ni = fp_inv(fp_add(t, pr_dpp<DPP_SWAP>(t)));
-#endif
   const fp_t r = fp_mul(a.v, ni);
   return pr_make(fp_sel(pr_odd(), fp_neg(r), r));
 }
@@ -437,13 +414,10 @@ __device__ inline fp2p_t fp2_inv(const fp2p_t a) {
 // a^((q-3)/4) = a^(q >> 2) for an a held on both lanes of the pair, right to left: the even lane
 // squares a^(2^i), the odd lane multiplies the set bits' powers (broadcast by DPP) into the
 // product, so each of the 379 exponent bits costs one product time, against 375 squarings + 86
-// products when both lanes run fp_pow_qm3d4's window chain (BLS_POW_PAIR=0).  The exponent is a
-// constant: the bit tests are wave-uniform (scalar branches).  Result on both lanes.
-#ifndef BLS_POW_PAIR
-#define BLS_POW_PAIR 1
-#endif
+// products when both lanes run fp_pow_qm3d4's window chain (HISTORY.md, "Square roots on the lane
+// pair").  The exponent is a constant: the bit tests are wave-uniform (scalar branches).  Result on
+// both lanes.
 __device__ __noinline__ fp_t fp_pow_qm3d4_pair(const fp_t a) {
-#if BLS_POW_PAIR
   const bool odd = pr_odd();
   fp_t r = odd ? FP_ONE_M : a;   // even lane: a^(2^i); odd lane: the running product
 #pragma unroll 1
@@ -456,9 +430,6 @@ __device__ __noinline__ fp_t fp_pow_qm3d4_pair(const fp_t a) {
       r = fp_sel(odd, r, fp_sqr(r));
   }
   return pr_dpp<DPP_ODD>(r);
-#else
-  return fp_pow_qm3d4(a);
-#endif
 }
 
 __device__ __forceinline__ bool fp_sqrt_pair(fp_t& r, const fp_t& a) {

@@ -248,12 +248,9 @@ BLS_INLINE cyc_bc<E> cyc_compress(const fp12_g<E>& f) {
   cyc_bc<E> g; g.g2 = f.c1.c0; g.g3 = f.c0.c2; g.g4 = f.c0.c1; g.g5 = f.c1.c2; return g;
 }
 
-// BLS_LAZY_CSQR=1: each output coefficient is one lazily reduced sum of products
-// (bls381_lazy.hpp): 10 products and 4 reductions per lane instead of 6 Fp2 squarings
-// (12 reductions) and 11 reduced linear combinations.
-#ifndef BLS_LAZY_CSQR
-#define BLS_LAZY_CSQR 1
-#endif
+// The compressed squaring: each output coefficient is one lazily reduced sum of products
+// (bls381_lazy.hpp): 10 products and 4 reductions per lane instead of the eager form's 6 Fp2
+// squarings (12 reductions) and 11 reduced linear combinations.
 
 // the one-lane representation: the per-lane functions once per coefficient
 BLS_INLINE cyc_bc<fp2_t> cyc_csqr_lazy(const cyc_bc<fp2_t>& g) {
@@ -273,20 +270,7 @@ BLS_INLINE cyc_bc<fp2_t> cyc_csqr_lazy(const cyc_bc<fp2_t>& g) {
 
 template <class E>
 BLS_INLINE cyc_bc<E> cyc_csqr(const cyc_bc<E>& g) {
-#if BLS_LAZY_CSQR
   return cyc_csqr_lazy(g);   // fp2p_t: bls381_pair.hpp
-#else
-  cyc_bc<E> r;
-  {
-    const E t0 = fp2_sqr(g.g4), t1 = fp2_sqr(g.g5), t2 = fp2_sqr(fp2_add(g.g4, g.g5));
-    r.g2 = fp2_3p2(fp2_mul_xi(fp2_sub2(t2, t0, t1)), g.g2);   // 6 xi g4 g5 + 2 g2
-    r.g3 = fp2_3m2(fp2_add_mul_xi(t0, t1), g.g3);             // 3 (g4^2 + xi g5^2) - 2 g3
-  }
-  const E t3 = fp2_sqr(g.g2), t4 = fp2_sqr(g.g3), t5 = fp2_sqr(fp2_add(g.g2, g.g3));
-  r.g4 = fp2_3m2(fp2_add_mul_xi(t3, t4), g.g4);               // 3 (g2^2 + xi g3^2) - 2 g4
-  r.g5 = fp2_3p2(fp2_sub2(t5, t3, t4), g.g5);                 // 6 g2 g3 + 2 g5
-  return r;
-#endif
 }
 
 // the full element from (g2..g5) and 1 / (4 g2)

@@ -134,17 +134,10 @@ __device__ __forceinline__ fq12_t fq12_two_lines(const fp2p_t& x0, const fp2p_t&
 // Returns conj(f_lo f_hi) (x < 0) in quad form.  `degenerate` (same on all four
 // lanes) is set when an active pair's running point reached infinity
 // (miller_loop_n: py_ecc's zero pairing value).
-#ifndef BLS_ML_QUAD_INLINE
-#define BLS_ML_QUAD_INLINE 0
-#endif
 // (operands and results by value: no pointer into the caller's private memory crosses the
 // call; the reference form below is a force-inlined wrapper)
 struct fq12_ml { fq12_t f; bool degenerate; };
-#if BLS_ML_QUAD_INLINE
-__device__ __forceinline__
-#else
 __device__ __noinline__
-#endif
 fq12_ml miller_loop_quad_run(const aff_t<fp2p_t> Q, const g1_line_pre P, bool active) {
   g2_proj<fp2p_t> T;
   T.x = Q.x; T.y = Q.y; T.z = e2_one<fp2p_t>();
@@ -565,10 +558,9 @@ __device__ __forceinline__ bool fq12_is_one(const fq12_t& f) {
   return qd_all(a & b & c);
 }
 
-// Karabina compressed squaring (cyc_csqr) on a quad.  lo holds (x, y) = (g4, g5)
-// and squares them (t0, t1, t2 of cyc_csqr), hi holds (g2, g3) (t3, t4, t5); each
-// half's outputs update the other half's pair, so one exchange per squaring:
-// three Fp2 squarings per lane instead of six.
+// Karabina compressed squaring (cyc_csqr) on a quad.  lo holds (x, y) = (g4, g5),
+// hi holds (g2, g3); each half's outputs update the other half's pair, so one
+// exchange per squaring: two of cyc_csqr's four lazily reduced sums per lane.
 struct cq_t { fp2p_t x, y; };
 
 __device__ __forceinline__ cq_t cq_compress(const fq12_t& f) {
@@ -581,7 +573,6 @@ __device__ __forceinline__ cq_t cq_compress(const fq12_t& f) {
 
 __device__ __forceinline__ cq_t cq_sqr(const cq_t& g) {
   const bool hi = qd_hi();
-#if BLS_LAZY_CSQR
   // lazy reduction (bls381_lazy.hpp): each half forms its two outputs from its own (x, y)
   // as wide sums -- S = x^2 + xi y^2 and lo: xi x y, hi: x y -- one reduction each
   const bool p = pr_odd();
@@ -613,17 +604,6 @@ __device__ __forceinline__ cq_t cq_sqr(const cq_t& g) {
   r.x = pr_make(fp_6p2_3m2(hi, Po, So, g.x.v));
   r.y = pr_make(fp_6p2_3m2(!hi, Po, So, g.y.v));
   return r;
-#else
-  const fp2p_t s0 = fp2_sqr(g.x), s1 = fp2_sqr(g.y), s2 = fp2_sqr(fp2_add(g.x, g.y));
-  const fp2p_t D = fp2_sub2(s2, s0, s1);       // 2 x y
-  const fp2p_t S = fp2_add_mul_xi(s0, s1);     // x^2 + xi y^2
-  const fp2p_t U = qd_swap(qd_sel(hi, S, fp2_mul_xi(D)));   // lo <- S(hi), hi <- xi D(lo)
-  const fp2p_t V = qd_swap(qd_sel(hi, D, S));               // lo <- D(hi), hi <- S(lo)
-  cq_t r;
-  r.x = fp2_3pm2(U, g.x, !hi);   // lo: g4' = 3 (g2^2 + xi g3^2) - 2 g4;  hi: g2' = 6 xi g4 g5 + 2 g2
-  r.y = fp2_3pm2(V, g.y, hi);    // lo: g5' = 6 g2 g3 + 2 g5;             hi: g3' = 3 (g4^2 + xi g5^2) - 2 g3
-  return r;
-#endif
 }
 
 // g2 of a compressed value, on all four lanes

@@ -1,5 +1,5 @@
 """Model of k_hash_cand_1's pooled try-and-increment search (bls381_kernels.hpp,
-BLS_HASH_COMPACT): the lane assignment and per-item resolution, simulated for a 64-lane wave
+dev_hash_cand_1): the lane assignment and per-item resolution, simulated for a 64-lane wave
 over random square patterns.  Each item must end with its lowest square offset -- the
 spec's candidate order (bls_signature.md:74-86) -- whatever the other items do, and the
 wave must finish in far fewer rounds than a lane-per-item loop's slowest item.
