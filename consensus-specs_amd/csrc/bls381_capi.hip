@@ -26,6 +26,7 @@
 #include "bls381.h"
 #include "bls381_kernels.hpp"
 #include "bls381_plan.hpp"
+#include "bls381_scope.hpp"
 
 using namespace bls381;
 
@@ -46,30 +47,19 @@ int check_subgroups() { return current_policy() == BLS381_POLICY_STRICT ? 1 : 0;
 // (SURVEY.md A.4), the strict policy with the spec's (bls_signature.md:47-52,58-64)
 int policy_flags(int sub) { return sub | (current_policy() == BLS381_POLICY_PYECC ? CHK_LAX : 0); }
 
-// Host memory that an async copy still reads: released once an event
-// recorded after the copy has completed (device-pointer entry points return
-// without synchronising, so a plan on the C++ stack would die too early).
-struct Keep {
-  hipEvent_t ev;
-  std::shared_ptr<void> data;
-};
-
+// (Streams, Fork, KeepList, Held: bls381_scope.hpp)
 struct Ctx {
   int device = -1;
-  hipStream_t stream = nullptr;
-  // side stream + fork/join events: independent stages of one batch run concurrently
-  hipStream_t side = nullptr, side2 = nullptr;
-  // high-priority stream: small latency-bound launches whose waves should be dispatched
-  // ahead of a large launch queued at the same time on another stream
-  hipStream_t prio = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_join3 = nullptr;
-  std::mutex fork_mu;
+  size_t simds = 0;   // CUs x 4
+  Streams q;
   void* ws = nullptr;
   size_t ws_cap = 0;
   std::mutex mu;
-  std::mutex keep_mu;
-  std::deque<Keep> keep;
+  KeepList keep;
+  ~Ctx() { streams_destroy(q); }
 };
+// the SIMD count of the device this thread's last get_ctx selected (256 CUs until then)
+thread_local size_t t_simds = 1024;
 
 std::mutex g_mu;
 std::vector<Ctx*> g_ctx;
@@ -77,7 +67,7 @@ std::vector<Ctx*> g_ctx;
 // ---- profiling: per-kernel HIP events on the launch stream
 struct ProfEv { const char* name; hipEvent_t a, b; };
 std::mutex g_prof_mu;
-bool g_prof_on = false;
+std::atomic<bool> g_prof_on{false};
 std::vector<ProfEv> g_prof_pending;
 std::map<std::string, std::pair<long, double>> g_prof_acc;
 
@@ -115,49 +105,21 @@ Ctx* get_ctx(int* rc) {
       *rc = BLS381_ENODEV;
       return nullptr;
     }
-    Ctx* c = new Ctx();
+    std::unique_ptr<Ctx> c(new Ctx());
     c->device = dev;
-    int prio_lo = 0, prio_hi = 0;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess ||
-        hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
-        hipStreamCreateWithPriority(&c->prio, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join3, hipEventDisableTiming) != hipSuccess) {
-      delete c; t_err = "stream create failed"; *rc = BLS381_EHIP; return nullptr;
-    }
-    g_ctx[dev] = c;
+    c->simds = (size_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * 4;
+    if (streams_create(c->q) != hipSuccess) { t_err = "stream create failed"; *rc = BLS381_EHIP; return nullptr; }
+    g_ctx[dev] = c.release();
   }
   if (hipSetDevice(dev) != hipSuccess) { t_err = "hipSetDevice failed"; *rc = BLS381_ENODEV; return nullptr; }
+  t_simds = g_ctx[dev]->simds;
   *rc = 0;
   return g_ctx[dev];
 }
 
-// Keeps `data` alive until the work queued on `s` so far has completed.
-int keep_until_done(Ctx* c, hipStream_t s, std::shared_ptr<void> data) {
-  std::lock_guard<std::mutex> lk(c->keep_mu);
-  while (!c->keep.empty() && hipEventQuery(c->keep.front().ev) == hipSuccess) {
-    (void)hipEventDestroy(c->keep.front().ev);
-    c->keep.pop_front();
-  }
-  hipEvent_t ev;
-  HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev, s);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    (void)hipEventDestroy(ev);
-    return fail("hipEventRecord", e);
-  }
-  c->keep.push_back({ev, std::move(data)});
-  return 0;
-}
-
 int ensure_ws(Ctx* c, size_t bytes) {
   if (c->ws_cap >= bytes) return 0;
-  if (c->ws) { HIPC(hipStreamSynchronize(c->stream)); HIPC(hipFree(c->ws)); c->ws = nullptr; c->ws_cap = 0; }
+  if (c->ws) { HIPC(hipStreamSynchronize(c->q.main)); HIPC(hipFree(c->ws)); c->ws = nullptr; c->ws_cap = 0; }
   size_t cap = bytes + bytes / 4 + (1 << 20);
   HIPC(hipMalloc(&c->ws, cap));
   c->ws_cap = cap;
@@ -187,12 +149,18 @@ int carve_ws(Ctx* c, Carve&& carve) {
 }
 
 // The frame of a host-pointer entry point: the context with its lock held, the context
-// workspace carved by the entry, copies in and out on the context stream, one synchronise.
+// workspace carved by the entry, copies in and out on the context stream, one synchronise --
+// finish(), or the destructor on every other way out, so the lock is never released with copies
+// from or to the caller's buffers still queued.
 struct HostCall {
   Ctx* c;
   std::unique_lock<std::mutex> lk;
   hipStream_t s;
-  explicit HostCall(Ctx* ctx) : c(ctx), lk(ctx->mu), s(ctx->stream) {}
+  bool finished = false;
+  explicit HostCall(Ctx* ctx) : c(ctx), lk(ctx->mu), s(ctx->q.main) {}
+  ~HostCall() {
+    if (!finished) (void)hipStreamSynchronize(s);
+  }
   template <class Carve> int carve(Carve&& cv) { return carve_ws(c, cv); }
   int upload(void* dst, const void* src, size_t bytes) {
     if (bytes) HIPC(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
@@ -204,6 +172,7 @@ struct HostCall {
   }
   int finish() {
     HIPC(hipStreamSynchronize(s));
+    finished = true;
     return 0;
   }
 };
@@ -252,16 +221,7 @@ struct NoBalanceScope {
   NoBalanceScope() : prev(g_no_balance) { g_no_balance = true; }
   ~NoBalanceScope() { g_no_balance = prev; }
 };
-size_t chip_simds() {
-  static const size_t simds = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return (size_t)cus * 4;
-  }();
-  return simds;
-}
+size_t chip_simds() { return t_simds; }
 unsigned balance_lds(dim3 grid, dim3 block) {
   const size_t simds = chip_simds();
   const size_t lanes = (size_t)grid.x * grid.y * grid.z * block.x * block.y * block.z;
@@ -273,7 +233,7 @@ template <class K, class... A>
 int launch(const char* name, hipStream_t s, dim3 grid, dim3 block, K kern, A... args) {
   if (grid.x == 0) return 0;
   ProfEv ev{name, nullptr, nullptr};
-  const bool prof = g_prof_on;
+  const bool prof = g_prof_on.load(std::memory_order_relaxed);
   if (prof) {
     HIPC(hipEventCreate(&ev.a));
     HIPC(hipEventCreate(&ev.b));
@@ -403,7 +363,7 @@ int run_verify_batch(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* msgs, 
   const bool sig_in_loop = chk && n > BLS_ML_QUAD_MAX_N;
   const int pk_flags = policy_flags(chk), sig_flags = policy_flags(sig_in_loop ? 0 : chk);
   const bool wide = n <= BLS_HASH_WIDE_MAX_N;
-  std::lock_guard<std::mutex> lk(c->fork_mu);
+  Fork fk(c->q, s);
   if (!chk && !wide) {
     // py_ecc, throughput: the three one-lane stages as ONE launch whose workgroups take the three
     // roles in dispatch order, the hash search first (k_prologue_1); then the cofactor map
@@ -413,34 +373,29 @@ int run_verify_batch(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* msgs, 
     LAUNCH("hash_bp", s, g2, b, k_hash_bp, n, w.h_aff, (uint8_t*)nullptr);
     return run_verify_pairings(n, w, verdicts, s, sig_in_loop);
   }
-  HIPC(hipEventRecord(c->ev_fork, s));
-  HIPC(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-  LAUNCH("decode_g1", c->side, g, b, k_decode_g1, n, pks, w.pk_aff, w.pk_st, pk_flags);
+  HIPC(fk.branch(c->q.side));
+  LAUNCH("decode_g1", c->q.side.stream, g, b, k_decode_g1, n, pks, w.pk_aff, w.pk_st, pk_flags);
   if (!chk) {
     // py_ecc, small batches: decode_g2 on a second side stream, and the wide search first (16
     // candidates per message in one round), so the hash does not wait for the batch's slowest
     // sequential search
-    HIPC(hipStreamWaitEvent(c->side2, c->ev_fork, 0));
-    LAUNCH("decode_g2_1", c->side2, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st, sig_flags);
-    HIPC(hipEventRecord(c->ev_join2, c->side2));
-    HIPC(hipEventRecord(c->ev_join, c->side));
+    HIPC(fk.branch(c->q.side2));
+    LAUNCH("decode_g2_1", c->q.side2.stream, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st, sig_flags);
     LAUNCH("hash_search", s, dim3(grid_for(16 * n)), b, k_hash_search<16>, n, msgs, (uint32_t)32, doms, 8, w.koff);
     TRY(launch_hash_koff(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr, (const uint32_t*)w.koff, 0));
-    HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
-    HIPC(hipStreamWaitEvent(s, c->ev_join2, 0));
+    HIPC(fk.join());
     return run_verify_pairings(n, w, verdicts, s, sig_in_loop);
   }
   // strict: both decodes in sequence on the side stream beside hash_to_G2 (decode_g1 carries the G1
   // subgroup test, and waiting for it before the cofactor map costs more than sharing the chip)
-  LAUNCH("decode_g2_1", c->side, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st, sig_flags);
-  HIPC(hipEventRecord(c->ev_join, c->side));
+  LAUNCH("decode_g2_1", c->q.side.stream, g, b, k_decode_g2_1, n, sigs, w.sig_aff, w.sig_st, sig_flags);
   if (wide) {
     LAUNCH("hash_search", s, dim3(grid_for(16 * n)), b, k_hash_search<16>, n, msgs, (uint32_t)32, doms, 8, w.koff);
     TRY(launch_hash_koff(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr, (const uint32_t*)w.koff, 0));
   } else {
     TRY(launch_hash_g2(s, n, msgs, 32u, doms, 8, w.h_aff, (uint8_t*)nullptr));
   }
-  HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
+  HIPC(fk.join());
   return run_verify_pairings(n, w, verdicts, s, sig_in_loop);
 }
 
@@ -749,10 +704,9 @@ int run_vm_batch(Ctx* c, const VmPlan& pl, size_t mlen, const uint8_t* d_pks, co
   // signature decodes run on the side stream while the main stream hashes the
   // messages; the Miller loops wait for both.
   {
-    std::lock_guard<std::mutex> fk(c->fork_mu);
-    hipStream_t side = c->side;
-    HIPC(hipEventRecord(c->ev_fork, s));
-    HIPC(hipStreamWaitEvent(side, c->ev_fork, 0));
+    Fork fk(c->q, s);
+    hipStream_t side = c->q.side.stream, side2 = c->q.side2.stream;
+    HIPC(fk.branch(c->q.side));
     if (G > 0) {
       // members in group order, then group sums -> affine
       const size_t nk = pl.key_idx.size();
@@ -771,22 +725,20 @@ int run_vm_batch(Ctx* c, const VmPlan& pl, size_t mlen, const uint8_t* d_pks, co
       b.off += used;
       LAUNCH("agg_g1_affine", side, dim3(grid_for(G)), dim3(KBLOCK), k_agg_g1_affine, G, jac, bad, agg_aff, agg_st);
     }
-    HIPC(hipEventRecord(c->ev_join, side));
     // the signature decodes on a second side stream: for an epoch of attestations the group
     // sums and the decodes are each about as long as the hash, so in sequence they would
     // outlast it
-    HIPC(hipStreamWaitEvent(c->side2, c->ev_fork, 0));
-    LAUNCH("decode_g2", c->side2, dim3(grid_for(2 * ncalls)), dim3(KBLOCK), k_decode_g2, ncalls, d_sigs, sig_aff,
+    HIPC(fk.branch(c->q.side2));
+    LAUNCH("decode_g2", side2, dim3(grid_for(2 * ncalls)), dim3(KBLOCK), k_decode_g2, ncalls, d_sigs, sig_aff,
            sig_st, policy_flags(chk));
     if (!pl.tasks) {
       // large batches: the signature pairs run here, beside hash_to_G2, so the group pairs fill
       // whole quads and the main Miller launch has no partial last round of waves
-      LAUNCH("miller_sig_tasks", c->side2, dim3(grid_for(4 * ncalls)), dim3(KBLOCK), k_miller_tasks<4>, ncalls,
+      LAUNCH("miller_sig_tasks", side2, dim3(grid_for(4 * ncalls)), dim3(KBLOCK), k_miller_tasks<4>, ncalls,
              (const int32_t*)d_stask, G, (const uint32_t*)h_aff, (const uint8_t*)h_st, (const uint32_t*)agg_aff,
              (const uint8_t*)agg_st, ncalls, (const uint32_t*)sig_aff, (const uint8_t*)sig_st,
              (const uint32_t*)d_sslot, nf, f, st);
     }
-    HIPC(hipEventRecord(c->ev_join2, c->side2));
     if (G > 0) {
       LAUNCH("gather_domains", s, dim3(grid_for(8 * G)), dim3(KBLOCK), k_gather_rows, G, (const uint32_t*)d_gcall,
              d_doms, 8u, d_gdom);
@@ -800,8 +752,7 @@ int run_vm_batch(Ctx* c, const VmPlan& pl, size_t mlen, const uint8_t* d_pks, co
                                            h_aff, h_st, (const uint32_t*)(wide ? d_koff : nullptr), pl.tasks ? 1 : 0))
         return rc_h;
     }
-    HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
-    HIPC(hipStreamWaitEvent(s, c->ev_join2, 0));
+    HIPC(fk.join());
   }
   if (pl.tasks) {
     // one octet per pair task while the tasks fit one wave per SIMD, else (or BLS381_ML_OCTET=0) one quad
@@ -860,21 +811,10 @@ void bls381_shutdown(void) {
   for (Ctx* c : g_ctx) {
     if (!c) continue;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->q.main);
     (void)hipDeviceSynchronize();
-    for (auto& k : c->keep) (void)hipEventDestroy(k.ev);
-    c->keep.clear();
+    keep_clear(c->keep);
     if (c->ws) (void)hipFree(c->ws);
-    (void)hipStreamDestroy(c->stream);
-    (void)hipStreamSynchronize(c->side);
-    (void)hipStreamSynchronize(c->side2);
-    (void)hipStreamSynchronize(c->prio);
-    (void)hipStreamDestroy(c->side);
-    (void)hipStreamDestroy(c->side2);
-    (void)hipStreamDestroy(c->prio);
-    (void)hipEventDestroy(c->ev_fork);
-    (void)hipEventDestroy(c->ev_join);
-    (void)hipEventDestroy(c->ev_join2);
     delete c;
   }
   g_ctx.clear();
@@ -900,7 +840,7 @@ int bls381_get_thread_subgroup_policy(void) { return current_policy(); }
 
 int bls381_profile_enable(int on) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
-  g_prof_on = on != 0;
+  g_prof_on.store(on != 0, std::memory_order_relaxed);
   g_prof_acc.clear();
   for (auto& e : g_prof_pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   g_prof_pending.clear();
@@ -1009,7 +949,8 @@ static int vm_host(HostCall& hc, size_t n_calls, const uint32_t* call_off, const
                    size_t msg_len, const uint8_t* sigs, const uint8_t* dom8s, const int* with_sig, Bump& b,
                    uint32_t** f, uint8_t** st) {
   const size_t nk = call_off[n_calls];
-  auto pl = std::make_shared<VmPlan>(plan_vm(n_calls, call_off, msgs, msg_len, pks, sigs, with_sig));
+  // the plan's arrays are async copy sources
+  Held<VmPlan> pl(hc.c->keep, hc.s, plan_vm(n_calls, call_off, msgs, msg_len, pks, sigs, with_sig));
   const size_t ws_bytes = vm_ws_bound(*pl, msg_len);
   uint8_t *d_pks, *d_sigs, *d_doms, *ws;
   TRY(hc.carve([&](Bump& in) {
@@ -1022,8 +963,7 @@ static int vm_host(HostCall& hc, size_t n_calls, const uint32_t* call_off, const
   TRY(hc.upload(d_pks, pks, 48 * nk));
   TRY(hc.upload(d_sigs, sigs, 96 * n_calls));
   TRY(hc.upload(d_doms, dom8s, 8 * n_calls));
-  TRY(run_vm_batch(hc.c, *pl, msg_len, d_pks, d_sigs, d_doms, b, hc.s, f, st));
-  return keep_until_done(hc.c, hc.s, pl);   // the plan's arrays are async copy sources
+  return run_vm_batch(hc.c, *pl, msg_len, d_pks, d_sigs, d_doms, b, hc.s, f, st);
 }
 
 int bls381_verify_multiple_batch(size_t n_calls, const uint32_t* call_off, const uint8_t* pks,
@@ -1068,14 +1008,14 @@ int bls381_verify_multiple_batch_device(size_t n_calls, const uint32_t* h_call_o
     for (size_t k = 0; k < n_calls; ++k)
       if (h_call_off[k + 1] < h_call_off[k]) return BLS381_EARG;
     std::vector<int> with_sig(n_calls, 1);
-    auto pl = std::make_shared<VmPlan>(plan_vm(n_calls, h_call_off, h_msgs, msg_len, nullptr, nullptr, with_sig.data()));
     hipStream_t s = (hipStream_t)stream;
+    Held<VmPlan> pl(c->keep, s, plan_vm(n_calls, h_call_off, h_msgs, msg_len, nullptr, nullptr, with_sig.data()));
     Bump b(d_workspace, bls381_verify_multiple_batch_workspace_size(n_calls, nk, msg_len));
     uint32_t* f;
     uint8_t* st;
     if ((rc = run_vm_batch(c, *pl, msg_len, d_pks, d_sigs, d_dom8s, b, s, &f, &st))) return rc;
     LAUNCH_FE(s, n_calls, f, st, d_verdicts);
-    return keep_until_done(c, s, pl);   // the plan's arrays are async copy sources
+    return 0;
   });
 }
 
@@ -1105,14 +1045,14 @@ static int vm_grouped_device(Ctx* c, size_t n_calls, const uint32_t* h_call_grou
                              const uint32_t* h_group_key_off, const uint8_t* h_group_msgs, size_t msg_len,
                              const uint8_t* d_keys, const uint8_t* d_sigs, const uint8_t* d_dom8s, uint8_t* d_verdicts,
                              void* d_workspace, void* stream, const agg_reg_src* reg) {
-  auto pl = std::make_shared<VmPlan>(plan_vm_grouped(n_calls, h_call_group_off, h_group_key_off, h_group_msgs, msg_len));
   hipStream_t s = (hipStream_t)stream;
+  Held<VmPlan> pl(c->keep, s, plan_vm_grouped(n_calls, h_call_group_off, h_group_key_off, h_group_msgs, msg_len));
   Bump b(d_workspace, bls381_verify_multiple_grouped_workspace_size(n_calls, n_groups, h_group_key_off[n_groups], msg_len));
   uint32_t* f;
   uint8_t* st;
   TRY(run_vm_batch(c, *pl, msg_len, d_keys, d_sigs, d_dom8s, b, s, &f, &st, reg));
   LAUNCH_FE(s, n_calls, f, st, d_verdicts);
-  return keep_until_done(c, s, pl);   // the plan's arrays are async copy sources
+  return 0;
 }
 
 int bls381_verify_multiple_grouped_device(size_t n_calls, const uint32_t* h_call_group_off, size_t n_groups,
@@ -1189,8 +1129,8 @@ int bls381_final_verify(size_t k, const uint8_t* parts576) {
     int rc = 0;
     Ctx* c = get_ctx(&rc);
     if (!c) return rc;
+    const auto passes = plan_products({0u, (uint32_t)k});   // outlives hc, which synchronises on every way out
     HostCall hc(c);
-    const auto passes = plan_products({0u, (uint32_t)k});   // alive until finish()
     uint8_t *d_in, *st, *d_v;
     uint32_t* f;
     Bump pb;   // the product passes' slices
@@ -1226,7 +1166,7 @@ static int agg_batch_impl(Ctx* c, int is_g2, size_t ng, const uint32_t* offsets,
   for (size_t g = 0; g < ng; ++g)
     if (offsets[g + 1] < offsets[g]) { t_err = "offsets not monotone"; return BLS381_EARG; }
   // the chunk lists are async-copy sources: they live until the stream passes them
-  auto hold = std::make_shared<AggPlan>(plan_agg(ng, offsets, is_g2 ? 2 : 1));
+  Held<AggPlan> hold(c->keep, s, plan_agg(ng, offsets, is_g2 ? 2 : 1));
   const AggPlan& plan = *hold;
   const uint32_t* jac;
   const uint8_t* bad;
@@ -1239,7 +1179,7 @@ static int agg_batch_impl(Ctx* c, int is_g2, size_t ng, const uint32_t* offsets,
     if ((rc = run_agg<fp_t>(plan, ng, d_pts, ws, s, &jac, &bad, &used, ws_cap, nullptr, flags))) return rc;
     LAUNCH("agg_compress", s, dim3(grid_for(ng)), dim3(KBLOCK), k_agg_compress<fp_t>, ng, jac, bad, d_out, d_status);
   }
-  return keep_until_done(c, s, hold);
+  return 0;
 }
 
 static size_t agg_ws_bytes(int is_g2, size_t ng, const uint32_t* offsets) {
@@ -1478,7 +1418,7 @@ int bls381_registry_create(size_t capacity, bls381_registry** out) {
     t_err = "registry allocation failed";
     return BLS381_EHIP;
   }
-  if (hipMemsetAsync(r->table, 0xFF, 4 * t, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+  if (hipMemsetAsync(r->table, 0xFF, 4 * t, c->q.main) != hipSuccess || hipStreamSynchronize(c->q.main) != hipSuccess) {
     registry_free(r);
     t_err = "registry init failed";
     return BLS381_EHIP;
@@ -1491,7 +1431,7 @@ void bls381_registry_destroy(bls381_registry* reg) {
   if (!reg) return;
   int rc = 0;
   Ctx* c = get_ctx(&rc);
-  if (c) (void)hipStreamSynchronize(c->stream);
+  if (c) (void)hipStreamSynchronize(c->q.main);
   registry_free(reg);
 }
 
@@ -1510,11 +1450,12 @@ int bls381_registry_add(bls381_registry* reg, size_t n, const uint8_t* pks48, in
   Ctx* c = registry_ctx(reg, &rc);
   if (!c) return rc;
   std::lock_guard<std::mutex> lr(reg->mu);
-  std::lock_guard<std::mutex> lk(c->mu);
+  std::vector<int32_t> res(n);   // outlives hc, which synchronises on every way out
+  HostCall hc(c);
   if (reg->size + n > reg->cap) { t_err = "registry capacity exceeded"; return BLS381_EARG; }
-  hipStream_t s = c->stream;
+  hipStream_t s = hc.s;
   const size_t first = reg->size;
-  HIPC(hipMemcpyAsync(reg->keys + 48 * first, pks48, 48 * n, hipMemcpyHostToDevice, s));
+  TRY(hc.upload(reg->keys + 48 * first, pks48, 48 * n));
   LAUNCH("registry_decode", s, dim3(grid_for(n)), dim3(KBLOCK), k_reg_decode, first, n, reg->cap,
          (const uint8_t*)reg->keys, reg->aff, reg->st);
   LAUNCH("registry_insert", s, dim3(grid_for(n)), dim3(KBLOCK), k_reg_insert, first, n, (const uint8_t*)reg->keys,
@@ -1522,9 +1463,8 @@ int bls381_registry_add(bls381_registry* reg, size_t n, const uint8_t* pks48, in
   LAUNCH("registry_lookup", s, dim3(grid_for(n)), dim3(KBLOCK), k_reg_lookup, n,
          (const uint8_t*)(reg->keys + 48 * first), (const uint8_t*)reg->keys, (const uint32_t*)reg->table, reg->tmask,
          reg->tmp);
-  std::vector<int32_t> res(n);
-  HIPC(hipMemcpyAsync(res.data(), reg->tmp, 4 * n, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
+  TRY(hc.download(res.data(), reg->tmp, 4 * n));
+  TRY(hc.finish());
   reg->size += n;
   int nbad = 0;
   for (size_t i = 0; i < n; ++i) nbad += res[i] < 0;
@@ -1570,7 +1510,7 @@ static int registry_agg_impl(Ctx* c, bls381_registry* reg, size_t ng, const uint
            (const uint8_t*)reg->keys, (const uint32_t*)reg->table, reg->tmask, e);
     d_entry = e;
   }
-  auto hold = std::make_shared<AggPlan>(plan_agg(ng, offsets));
+  Held<AggPlan> hold(c->keep, s, plan_agg(ng, offsets));
   const agg_reg_src src{d_entry, reg->aff, reg->st, reg->cap, reg->size};
   const uint32_t* jac;
   const uint8_t* bad;
@@ -1579,7 +1519,7 @@ static int registry_agg_impl(Ctx* c, bls381_registry* reg, size_t ng, const uint
                          policy_flags(0));
   if (rc) return rc;
   LAUNCH("agg_compress", s, dim3(grid_for(ng)), dim3(KBLOCK), k_agg_compress<fp_t>, ng, jac, bad, d_out, d_status);
-  return keep_until_done(c, s, hold);
+  return 0;
 }
 
 size_t bls381_registry_aggregate_workspace_size(size_t n_groups, size_t n_in) {
@@ -1673,12 +1613,12 @@ size_t bls381_ssz_root_workspace_size(void) {
 
 static int ssz_root_impl(size_t n, const uint8_t* d_items, size_t stride, const uint32_t* h_prog, uint32_t plen,
                          uint8_t* d_roots, const SszWs& w, hipStream_t s, Ctx* c) {
-  auto prog = std::make_shared<std::vector<uint32_t>>(h_prog, h_prog + plen);
+  Held<std::vector<uint32_t>> prog(c->keep, s, std::vector<uint32_t>(h_prog, h_prog + plen));
   HIPC(hipMemcpyAsync(w.prog, prog->data(), 4 * plen, hipMemcpyHostToDevice, s));
   HIPC(hipMemsetAsync(w.err, 0, 4, s));
   LAUNCH("ssz_root", s, dim3(grid_for(n)), dim3(KBLOCK), k_ssz_root, n, d_items, stride, (const uint32_t*)w.prog,
          plen, d_roots, w.err);
-  return keep_until_done(c, s, prog);
+  return 0;
 }
 
 int bls381_ssz_root_batch_device(size_t n, const uint8_t* d_items, size_t stride, size_t item_size,
@@ -1884,11 +1824,10 @@ static int process_deposits_impl(Ctx* c, bls381_registry* reg, size_t n, const u
   const ProcessDepositsWs w = carve_process_deposits(b, n);
   const dim3 g(grid_for(n)), blk(KBLOCK);
   const uint32_t mask = (uint32_t)(w.slots - 1);
-  auto consts = std::make_shared<std::vector<uint8_t>>(40);
+  Held<std::vector<uint8_t>> consts(c->keep, s, std::vector<uint8_t>(40));
   std::memcpy(consts->data(), deposit_root, 32);
   std::memcpy(consts->data() + 32, dom8, 8);
   HIPC(hipMemcpyAsync(w.consts, consts->data(), 40, hipMemcpyHostToDevice, s));
-  TRY(keep_until_done(c, s, consts));
   HIPC(hipMemsetAsync(w.table, 0xFF, 4 * w.slots, s));
   HIPC(hipMemsetAsync(w.meta, 0xFF, 8, s));
   const uint8_t* d_data = d_deposits + DEPOSIT_PROOF_BYTES;
@@ -2143,9 +2082,9 @@ int bls381_attesting_entries_device(size_t n_att, const uint32_t* h_committee_of
       return BLS381_EARG;
     const size_t bitfield_bytes = h_bits_off[n_att];
     // the descriptors, and below the bitfields, in host blocks of the call's own: async copy sources
-    auto hold = std::make_shared<std::vector<att_desc>>(n_att);
+    std::vector<att_desc> desc(n_att);
     TRY(att_plan(n_att, h_committee_off, h_committee_len, h_bits_off, h_aggregation_bits, h_custody_bits, n_shuffled,
-                 h_group_key_off, h_ok, entries_cap, hold->data()));
+                 h_group_key_off, h_ok, entries_cap, desc.data()));
     const size_t total = h_group_key_off[2 * n_att];
     if (total == 0) return 0;
     if (!d_entries) return BLS381_EARG;
@@ -2155,7 +2094,8 @@ int bls381_attesting_entries_device(size_t n_att, const uint32_t* h_committee_of
     hipStream_t s = (hipStream_t)stream;
     Bump b(d_workspace, bls381_attesting_entries_workspace_size(n_att, bitfield_bytes));
     const AttWs w = carve_att(b, n_att, bitfield_bytes);
-    auto bits = std::make_shared<std::vector<uint8_t>>(2 * bitfield_bytes);
+    Held<std::vector<att_desc>> hold(c->keep, s, std::move(desc));
+    Held<std::vector<uint8_t>> bits(c->keep, s, std::vector<uint8_t>(2 * bitfield_bytes));
     std::memcpy(bits->data(), h_aggregation_bits, bitfield_bytes);
     std::memcpy(bits->data() + bitfield_bytes, h_custody_bits, bitfield_bytes);
     HIPC(hipMemcpyAsync(w.desc, hold->data(), n_att * sizeof(att_desc), hipMemcpyHostToDevice, s));
@@ -2163,8 +2103,7 @@ int bls381_attesting_entries_device(size_t n_att, const uint32_t* h_committee_of
     HIPC(hipMemcpyAsync(w.cust, bits->data() + bitfield_bytes, bitfield_bytes, hipMemcpyHostToDevice, s));
     LAUNCH("attesting_entries", s, dim3((unsigned)n_att), dim3(ATT_BLOCK), k_attesting_entries, (const att_desc*)w.desc,
            (const uint8_t*)w.agg, (const uint8_t*)w.cust, d_shuffled, d_entries);
-    TRY(keep_until_done(c, s, hold));
-    return keep_until_done(c, s, bits);
+    return 0;
   });
 }
 
@@ -2346,6 +2285,33 @@ int comm_alloc_rows(Comm* cm) {
   return 0;
 }
 
+// With g_comm_mu held: refuses a second communicator or more ranks than the row buffer serves,
+// and gives `fresh` its ranks, device and rows.
+int comm_prepare(Comm* fresh, int nranks, int rank, int device) {
+  if (g_comm.comm || g_comm.virt) { t_err = "communicator already initialised"; return BLS381_EARG; }
+  if (576 * ((size_t)nranks + 1) + 1024 > COMM_ROWS_BYTES) { t_err = "too many ranks"; return BLS381_EARG; }
+  fresh->nranks = nranks;
+  fresh->rank = rank;
+  fresh->device = device;
+  return comm_alloc_rows(fresh);
+}
+
+// The frame of a collective entry point: this thread's context, g_comm_mu held for the whole call,
+// the communicator, and RCCL unless the communicator is virtual.  rc != 0: the call cannot start.
+struct CommCall {
+  int rc = 0;
+  Ctx* c;
+  std::unique_lock<std::mutex> lk;
+  Comm* cm = nullptr;
+  RcclApi* api = nullptr;
+  CommCall() : c(get_ctx(&rc)) {
+    if (!c) return;
+    lk = std::unique_lock<std::mutex>(g_comm_mu);
+    if (!(cm = comm_ctx(&rc))) return;
+    if (!cm->virt && !(api = rccl_api())) rc = BLS381_ENODEV;
+  }
+};
+
 // the ranks whose rows this process computes: its own, or all of them (virtual)
 int first_rank(const Comm* cm) { return cm->virt ? 0 : cm->rank; }
 int last_rank(const Comm* cm) { return cm->virt ? cm->nranks - 1 : cm->rank; }
@@ -2384,10 +2350,8 @@ int bls381_comm_init(int nranks, int rank, const uint8_t uid[128]) {
   RcclApi* api = rccl_api();
   if (!api) return BLS381_ENODEV;
   std::lock_guard<std::mutex> lk(g_comm_mu);
-  if (g_comm.comm || g_comm.virt) { t_err = "communicator already initialised"; return BLS381_EARG; }
-  if (576 * ((size_t)nranks + 1) + 1024 > COMM_ROWS_BYTES) { t_err = "too many ranks"; return BLS381_EARG; }
   Comm fresh;
-  if ((rc = comm_alloc_rows(&fresh))) return rc;
+  if ((rc = comm_prepare(&fresh, nranks, rank, c->device))) return rc;
   ncclUniqueId id;
   std::memcpy(&id, uid, sizeof(id));
   ncclComm_t comm;
@@ -2397,11 +2361,8 @@ int bls381_comm_init(int nranks, int rank, const uint8_t uid[128]) {
     if (fresh.rows_ev) (void)hipEventDestroy(fresh.rows_ev);
     return nccl_fail(api, "ncclCommInitRank", nr);
   }
+  fresh.comm = comm;
   g_comm = fresh;
-  g_comm.comm = comm;
-  g_comm.nranks = nranks;
-  g_comm.rank = rank;
-  g_comm.device = c->device;
   return 0;
 }
 
@@ -2411,15 +2372,10 @@ int bls381_comm_init_virtual(int nranks) {
   Ctx* c = get_ctx(&rc);
   if (!c) return rc;
   std::lock_guard<std::mutex> lk(g_comm_mu);
-  if (g_comm.comm || g_comm.virt) { t_err = "communicator already initialised"; return BLS381_EARG; }
-  if (576 * ((size_t)nranks + 1) + 1024 > COMM_ROWS_BYTES) { t_err = "too many ranks"; return BLS381_EARG; }
   Comm fresh;
-  if ((rc = comm_alloc_rows(&fresh))) return rc;
+  if ((rc = comm_prepare(&fresh, nranks, 0, c->device))) return rc;
+  fresh.virt = true;
   g_comm = fresh;
-  g_comm.virt = true;
-  g_comm.nranks = nranks;
-  g_comm.rank = 0;
-  g_comm.device = c->device;
   return 0;
 }
 
@@ -2459,17 +2415,15 @@ void bls381_comm_destroy(void) {
 int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* msgs, size_t msg_len,
                                    const uint8_t sig[96], const uint8_t dom8[8]) {
   if ((n && (!pks || (!msgs && msg_len))) || !sig || !dom8 || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
+  CommCall cc;
+  if (cc.rc) return cc.rc;
+  Ctx* c = cc.c;
+  Comm* cm = cc.cm;
+  RcclApi* api = cc.api;
   int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> clk(g_comm_mu);
-  Comm* cm = comm_ctx(&rc);
-  if (!cm) return rc;
-  RcclApi* api = cm->virt ? nullptr : rccl_api();
-  if (!cm->virt && !api) return BLS381_ENODEV;
   HostCall hc(c);   // holds c->mu for the whole call
   const size_t R = (size_t)cm->nranks;
-  hipStream_t s = c->stream;
+  hipStream_t s = c->q.main;
   uint8_t* d_rows;
   if ((rc = comm_rows(cm, 576 * R + 576 + 64, &d_rows))) return rc;   // fits by construction (init)
   if (cm->rows_ev) (void)hipEventSynchronize(cm->rows_ev);   // a device-form call may still use them
@@ -2525,10 +2479,10 @@ int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* 
       uint8_t* gst = b.take<uint8_t>(R);
       HIPC(hipMemsetAsync(gst, ST_OK, R, s));
       LAUNCH("fp12_from_bytes", s, dim3(grid_for(2 * R)), dim3(KBLOCK), k_fp12_from_bytes, R, (const uint8_t*)d_rows, g);
-      auto passes = std::make_shared<ProductPasses>(plan_products({0u, (uint32_t)R}));
+      Held<ProductPasses> passes(c->keep, s, plan_products({0u, (uint32_t)R}));
       TRY(run_product_passes(b, s, *passes, g, gst, R));
       LAUNCH_FE(s, (size_t)1, g, gst, d_v);
-      return keep_until_done(c, s, passes);
+      return 0;
     });
     if (root) {
       (void)hipStreamSynchronize(s);
@@ -2539,7 +2493,7 @@ int bls381_verify_multiple_sharded(size_t n, const uint8_t* pks, const uint8_t* 
   if (!cm->virt) NCCLC(api, api->broadcast(d_v, d_v, 1, ncclUint8, 0, cm->comm, s));
   uint8_t v = 0;
   HIPC(hipMemcpyAsync(&v, d_v, 1, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
+  TRY(hc.finish());
   if (local) return local;
   return v ? 1 : 0;
 }
@@ -2635,7 +2589,7 @@ static int agg_sharded_impl(Ctx* c, Comm* cm, RcclApi* api, size_t n_local, cons
     // force_err: the caller could not stage its keys (d_workspace may be null): a flagged row only
     const int lrc = force_err ? force_err : guarded([&]() -> int {
       const uint32_t off1[2] = {0, (uint32_t)cnt};
-      auto hold = std::make_shared<AggPlan>(plan_agg(1, off1, 1));
+      Held<AggPlan> hold(c->keep, s, plan_agg(1, off1, 1));
       const uint32_t* jac;
       const uint8_t* bad;
       size_t used = 0;
@@ -2645,7 +2599,7 @@ static int agg_sharded_impl(Ctx* c, Comm* cm, RcclApi* api, size_t n_local, cons
                              policy_flags(0))))
         return e;
       LAUNCH("agg_jac_row", s, dim3(1), dim3(64), k_agg_jac_row, jac, bad, row);
-      return keep_until_done(c, s, hold);
+      return 0;
     });
     if (lrc) {
       (void)hipMemsetAsync(row, 0, row_b, s);                   // z = 0 and the bad flag set:
@@ -2680,33 +2634,25 @@ static int agg_sharded_impl(Ctx* c, Comm* cm, RcclApi* api, size_t n_local, cons
 int bls381_aggregate_pubkeys_sharded_device(size_t n_local, const uint8_t* d_pks, uint8_t* d_out48,
                                             int32_t* d_status, void* d_workspace, void* stream) {
   if (!d_out48 || !d_status || !d_workspace || (n_local && !d_pks)) return BLS381_EARG;
-  int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> clk(g_comm_mu);
-  Comm* cm = comm_ctx(&rc);
-  if (!cm) return rc;
-  RcclApi* api = cm->virt ? nullptr : rccl_api();
-  if (!cm->virt && !api) return BLS381_ENODEV;
-  return agg_sharded_impl(c, cm, api, n_local, d_pks, d_out48, d_status, d_workspace, (hipStream_t)stream);
+  CommCall cc;
+  if (cc.rc) return cc.rc;
+  return agg_sharded_impl(cc.c, cc.cm, cc.api, n_local, d_pks, d_out48, d_status, d_workspace, (hipStream_t)stream);
 }
 
 int bls381_aggregate_pubkeys_sharded(size_t n, const uint8_t* pks, uint8_t out[48]) {
   // the device form's protocol over this rank's contiguous range (sizes differing by at most one,
   // sharding.shard_range; a virtual communicator takes the whole call), copied in from host memory
   if (!out || (n && !pks)) return BLS381_EARG;
+  CommCall cc;
+  if (cc.rc) return cc.rc;
+  Ctx* c = cc.c;
+  Comm* cm = cc.cm;
+  RcclApi* api = cc.api;
   int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> clk(g_comm_mu);
-  Comm* cm = comm_ctx(&rc);
-  if (!cm) return rc;
-  RcclApi* api = cm->virt ? nullptr : rccl_api();
-  if (!cm->virt && !api) return BLS381_ENODEV;
   if (cm->rows_ev) (void)hipEventSynchronize(cm->rows_ev);   // a device-form call may still use the rows
   const size_t R = (size_t)cm->nranks;
-  std::lock_guard<std::mutex> lk(c->mu);
-  hipStream_t s = c->stream;
+  HostCall hc(c);
+  hipStream_t s = hc.s;
   const size_t base = n / R, extra = n % R, rr = (size_t)cm->rank;
   const size_t lo = cm->virt ? 0 : rr * base + (rr < extra ? rr : extra);
   const size_t cnt = cm->virt ? n : base + (rr < extra ? 1 : 0);
@@ -2730,9 +2676,9 @@ int bls381_aggregate_pubkeys_sharded(size_t n, const uint8_t* pks, uint8_t out[4
   rc = agg_sharded_impl(c, cm, api, local ? 0 : cnt, local ? nullptr : d_in, d_res, (int32_t*)(d_res + 48),
                         local ? nullptr : w, s, local);
   int32_t st = 0;
-  HIPC(hipMemcpyAsync(out, d_res, 48, hipMemcpyDeviceToHost, s));
-  HIPC(hipMemcpyAsync(&st, d_res + 48, 4, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
+  TRY(hc.download(out, d_res, 48));
+  TRY(hc.download(&st, d_res + 48, 4));
+  TRY(hc.finish());
   if (local) return local;
   return rc ? rc : st;
 }
@@ -2742,14 +2688,12 @@ int bls381_verify_multiple_batch_sharded(size_t n_calls, const uint32_t* call_of
                                          const uint8_t* dom8s, uint8_t* verdicts) {
   if (!call_off || !sigs || !dom8s || !verdicts || msg_len > BLS381_MSG_MAX) return BLS381_EARG;
   if (call_off[n_calls] && (!pks || (!msgs && msg_len))) return BLS381_EARG;
+  CommCall cc;
+  if (cc.rc) return cc.rc;
+  Ctx* c = cc.c;
+  Comm* cm = cc.cm;
+  RcclApi* api = cc.api;
   int rc = 0;
-  Ctx* c = get_ctx(&rc);
-  if (!c) return rc;
-  std::lock_guard<std::mutex> clk(g_comm_mu);
-  Comm* cm = comm_ctx(&rc);
-  if (!cm) return rc;
-  RcclApi* api = cm->virt ? nullptr : rccl_api();
-  if (!cm->virt && !api) return BLS381_ENODEV;
   const size_t R = (size_t)cm->nranks;
   const size_t base = n_calls / R, extra = n_calls % R, width = base + (extra ? 1 : 0);
   if (width == 0) return 0;
@@ -2774,7 +2718,7 @@ int bls381_verify_multiple_batch_sharded(size_t n_calls, const uint32_t* call_of
   }
   if (!cm->virt) {   // all-gather the verdict rows (each rank filled its own), through the comm buffer
     std::lock_guard<std::mutex> lk(c->mu);
-    hipStream_t s = c->stream;
+    hipStream_t s = c->q.main;
     uint8_t* d_rows;
     const size_t piece = std::min(width, COMM_ROWS_BYTES / (R + 1));
     if ((rc = comm_rows(cm, piece * (R + 1), &d_rows))) return rc;   // fits by construction
@@ -2853,7 +2797,9 @@ int run_verify_randomized(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* m
   uint8_t* d_seed = b.take<uint8_t>(64);
   const dim3 g1(grid_for(n)), g2(grid_for(2 * n)), blk(KBLOCK);
   const int chk = check_subgroups();
-  auto seed = std::make_shared<std::vector<uint8_t>>(seed32, seed32 + 32);
+  // async copy sources (the seed, the plan's chunk lists, the product passes below): held for
+  // the error returns -- the last line is reached with the stream synchronised
+  Held<std::vector<uint8_t>> seed(c->keep, s, std::vector<uint8_t>(seed32, seed32 + 32));
   HIPC(hipMemcpyAsync(d_seed, seed->data(), 32, hipMemcpyHostToDevice, s));
   HIPC(hipMemsetAsync(zeros, 0, n, s));
   // Miller values: B/2 item-pair slots per sub-batch + its signature-sum slot
@@ -2864,7 +2810,7 @@ int run_verify_randomized(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* m
   // per sub-batch sum of [r_i] sig_i (planned here; runs on the priority stream)
   std::vector<uint32_t> off(nb + 1);
   for (size_t k = 0; k <= nb; ++k) off[k] = (uint32_t)std::min(n, k * B);
-  auto plan = std::make_shared<AggPlan>(plan_agg(nb, off.data()));
+  Held<AggPlan> plan(c->keep, s, plan_agg(nb, off.data()));
   uint32_t* s_aff = b.take<uint32_t>(4 * FP_LIMBS * nb);
   uint8_t* s_st = b.take<uint8_t>(nb);
   {
@@ -2874,7 +2820,7 @@ int run_verify_randomized(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* m
     // form, their Miller loops) on the priority stream beside k_hash_bp and the item Miller loops.
     // Round 5's order (decode_g1, decode_g2 with the G2 test and the sums in sequence, then the pair
     // hash and k_rb_scale_g1) measured 2.36 against 2.43-2.53 M/s (r06b); removed.
-    std::lock_guard<std::mutex> lk(c->fork_mu);
+    Fork fk(c->q, s);
     LAUNCH("rb_prologue", s, dim3(3 * grid_for(n)), blk, k_prologue_1<1>, n, pks, sigs, msgs, (uint32_t)32, doms, 8,
            (const uint8_t*)d_seed, w.pk_aff, w.pk_st, w.sig_aff, w.sig_st, w.h_aff, r1, r1_st, policy_flags(chk),
            policy_flags(0));
@@ -2882,9 +2828,8 @@ int run_verify_randomized(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* m
            cls, chk);
     // the signature branch's window and combine chains and the sums' loops are latency-bound
     // launches of a few waves each: beside the full-chip ones on the main stream
-    HIPC(hipEventRecord(c->ev_fork, s));
-    HIPC(hipStreamWaitEvent(c->prio, c->ev_fork, 0));
-    hipStream_t sb = c->prio;
+    HIPC(fk.branch(c->q.prio));
+    hipStream_t sb = c->q.prio.stream;
     // BLS381_RB_MSM (measurement knob): 1 (default) the sub-batch sums sum_i [r_i] sig_i as one bucket
     // MSM per sub-batch (k_rb_msm_*); 0 a joint 32-bit ladder per item (k_rb_scale_g2) and a tree sum
     // The MSM gives each (sub-batch, window, digit) bucket to one lane pair, which adds its ~B/16
@@ -2920,13 +2865,10 @@ int run_verify_randomized(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* m
       b.off += used;
     }
     LAUNCH("agg_g2_affine", sb, dim3(grid_for(2 * nb)), blk, k_agg_g2_affine, nb, sjac, sbad, s_aff, s_st);
-    HIPC(hipEventRecord(c->ev_join, sb));
-    HIPC(hipStreamWaitEvent(c->prio, c->ev_join, 0));
     // (r06: the sums' loop waves at raised issue priority, s_setprio 3, slowed k_hash_bp beside them
     // from 3.6 to 5.4 ms: 2.47 against 2.60 M/s at B = 64, same box; removed)
-    LAUNCH("rb_miller_sig", c->prio, dim3(grid_for(4 * nb)), blk, k_rb_miller_sig, nb, hb, (const uint32_t*)s_aff,
+    LAUNCH("rb_miller_sig", sb, dim3(grid_for(4 * nb)), blk, k_rb_miller_sig, nb, hb, (const uint32_t*)s_aff,
            (const uint8_t*)s_st, nslots, f, fst);
-    HIPC(hipEventRecord(c->ev_join2, c->prio));
     // the cofactor map beside the signature branch
     LAUNCH("hash_bp", s, g2, blk, k_hash_bp, n, w.h_aff, w.f_st);
     // the batched items two per Miller accumulator: lines of both pairs on a quad, then f^2 L
@@ -2939,13 +2881,13 @@ int run_verify_randomized(Ctx* c, size_t n, const uint8_t* pks, const uint8_t* m
       LAUNCH("rb_miller_accum", s, dim3(grid_for(4 * cnt)), blk, k_ml_accum_q, nslots, q0, cnt, (const uint32_t*)mlL,
              (const uint8_t*)mlst, f, fst, hb);
     }
-    HIPC(hipStreamWaitEvent(s, c->ev_join2, 0));
+    HIPC(fk.join());
   }
   int rc = 0;
   std::vector<uint32_t> seg(nb + 1);
   for (size_t k = 0; k <= nb; ++k) seg[k] = (uint32_t)(k * (hb + 1));
-  const ProductPasses passes = plan_products(seg);   // alive until the synchronise below
-  TRY(run_product_passes(b, s, passes, f, fst, nslots));
+  Held<ProductPasses> passes(c->keep, s, plan_products(seg));
+  TRY(run_product_passes(b, s, *passes, f, fst, nslots));
   uint8_t* bv = b.take<uint8_t>(nb);
   LAUNCH_FE(s, nb, f, fst, bv);
   std::vector<uint8_t> h_bv(nb), h_cls(n);

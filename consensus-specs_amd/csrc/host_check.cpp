@@ -11,6 +11,8 @@
 //   G1 affine 96 B = x || y;  G2 affine 192 B = x || y (each Fp2)
 #include <cstring>
 #include <map>
+#include <mutex>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -20,6 +22,71 @@
 #include "bls381_plan.hpp"
 #include "bls381_shuffle.hpp"
 #include "bls381_ssz.hpp"
+
+// ---- stand-ins for the HIP types and runtime calls that bls381_scope.hpp is written against.
+// Every call appends one line to a log (hc_scope_scenario, at the end of this file, returns it);
+// the k-th call after a scenario's "begin" (destroys not counted) can be made to fail.  Internal linkage throughout: this
+// library is loaded into processes that also hold the real runtime and exports no hip* name.
+namespace {
+struct StandIn {
+  char kind;   // 'S' stream, 'E' event
+  int id;
+  bool complete = false;   // an event: what hipEventQuery reports (set by the scenario)
+};
+typedef StandIn* hipStream_t;
+typedef StandIn* hipEvent_t;
+typedef int hipError_t;
+constexpr hipError_t hipSuccess = 0, hipErrorNotReady = 600;
+constexpr unsigned hipStreamNonBlocking = 1, hipEventDisableTiming = 2;
+
+struct StandInState {
+  std::string log;
+  int next_id = 0, calls = 0, fail_at = 0;
+  bool counting = false;
+} g_si;
+
+void si_log(const std::string& line) { g_si.log += line + "\n"; }
+std::string si_name(const StandIn* h) { return h ? std::string(1, h->kind) + std::to_string(h->id) : "null"; }
+// logs the call; the failing call is logged as "FAIL <call>" and returns its own code, 1000 + k
+hipError_t si_call(const std::string& line) {
+  if (g_si.counting && ++g_si.calls == g_si.fail_at) {
+    si_log("FAIL " + line);
+    return 1000 + g_si.calls;
+  }
+  si_log(line);
+  return hipSuccess;
+}
+hipError_t si_create(char kind, const char* what, StandIn** out) {
+  StandIn* h = new StandIn{kind, g_si.next_id};
+  const hipError_t e = si_call(std::string(what) + " " + si_name(h));
+  if (e != hipSuccess) { delete h; return e; }
+  ++g_si.next_id;
+  *out = h;
+  return hipSuccess;
+}
+hipError_t si_destroy(const char* what, StandIn* h) {   // never the failing call: nothing could free h then
+  si_log(std::string(what) + " " + si_name(h));
+  delete h;
+  return hipSuccess;
+}
+
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return si_create('S', "stream_create", s); }
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { return si_create('S', "stream_create", s); }
+hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) {
+  *lo = 0;
+  *hi = -1;
+  return si_call("priority_range");
+}
+hipError_t hipStreamSynchronize(hipStream_t s) { return si_call("sync " + si_name(s)); }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { return si_call("wait " + si_name(s) + " " + si_name(e)); }
+hipError_t hipStreamDestroy(hipStream_t s) { return si_destroy("stream_destroy", s); }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return si_create('E', "event_create", e); }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { return si_call("record " + si_name(e) + " " + si_name(s)); }
+hipError_t hipEventQuery(hipEvent_t e) { return e->complete ? hipSuccess : hipErrorNotReady; }   // not logged
+hipError_t hipEventDestroy(hipEvent_t e) { return si_destroy("event_destroy", e); }
+}  // namespace
+
+#include "bls381_scope.hpp"
 
 using namespace bls381;
 
@@ -745,6 +812,106 @@ uint32_t hc_deposit_root_prog(uint32_t* out, size_t* item_size) {
   std::memcpy(out, DEPOSIT_ROOT_PROG, sizeof(DEPOSIT_ROOT_PROG));
   *item_size = DEPOSIT_BYTES;
   return DEPOSIT_ROOT_PROG_LEN;
+}
+
+// ---- the scopes of the host layer (bls381_scope.hpp) over the stand-ins at the top of this file
+}  // extern "C"
+namespace {
+void si_launch(hipStream_t s) { si_log("launch " + si_name(s)); }   // work queued by the scope's user
+struct Tracked {   // held data: its release shows in the log
+  const char* name;
+  ~Tracked() { if (name) si_log(std::string("released ") + name); }
+  Tracked(const char* n) : name(n) {}
+  Tracked(Tracked&& o) : name(o.name) { o.name = nullptr; }
+};
+
+// a pipeline that forks onto both side streams and is left by `how`: 0 its join, 1 an error
+// return before the join, 2 an exception before the join
+int fork_pipeline(Streams& q, hipStream_t s, int how) {
+  Fork fk(q, s);
+  si_launch(s);
+  if (fk.branch(q.side) != hipSuccess) return -1;
+  si_launch(q.side.stream);
+  if (fk.branch(q.side2) != hipSuccess) return -1;
+  si_launch(q.side2.stream);
+  si_launch(s);
+  if (how == 1) return -2;
+  if (how == 2) throw std::runtime_error("workspace bound exceeded");
+  si_log("join rc " + std::to_string(fk.join()));
+  si_launch(s);
+  si_log("join rc " + std::to_string(fk.join()));
+  return 0;
+}
+// an entry that holds data for a copy on `s` and is left by its last line (0) or an error return (1)
+int hold_entry(KeepList& keep, hipStream_t s, int how) {
+  Held<Tracked> data(keep, s, Tracked("data"));
+  si_launch(s);   // the copy that reads *data
+  if (how == 1) return -2;
+  si_launch(s);
+  return 0;
+}
+void si_complete_all(KeepList& keep) {
+  for (Keep& k : keep.items) k.ev->complete = true;
+  si_log("complete");
+}
+
+bool run_scenario(const std::string& name, int fail_at) {
+  StandIn caller{'S', -1};   // the caller's stream: not one of the context's
+  hipStream_t s = &caller;
+  g_si = StandInState();
+  g_si.fail_at = fail_at;
+  if (name == "streams") {
+    Streams q;
+    si_log("begin");
+    g_si.counting = true;
+    const hipError_t e = streams_create(q);
+    g_si.counting = false;
+    si_log("create rc " + std::to_string(e));
+    streams_destroy(q);   // after a failure: nothing left to destroy
+    si_log("end");
+    return true;
+  }
+  const bool is_fork = name == "fork" || name == "fork_return" || name == "fork_throw";
+  const bool is_hold = name == "hold" || name == "hold_return";
+  if (!is_fork && !is_hold) return false;
+  Streams q;
+  if (streams_create(q) != hipSuccess) return false;
+  si_log("begin");
+  g_si.counting = true;
+  if (is_fork) {
+    try {
+      si_log("pipeline rc " + std::to_string(fork_pipeline(q, s, name == "fork" ? 0 : name == "fork_return" ? 1 : 2)));
+    } catch (const std::exception& e) {
+      si_log(std::string("caught ") + e.what());
+    }
+  } else {
+    KeepList keep;
+    si_log("entry rc " + std::to_string(hold_entry(keep, s, name == "hold" ? 0 : 1)));
+    // later entries on the same context: each one first releases what has completed
+    { Held<Tracked> next(keep, s, Tracked("next")); }
+    si_complete_all(keep);
+    { Held<Tracked> last(keep, s, Tracked("last")); }
+    g_si.counting = false;
+    si_log("shutdown");
+    keep_clear(keep);
+  }
+  g_si.counting = false;
+  si_log("end");
+  streams_destroy(q);
+  return true;
+}
+}  // namespace
+extern "C" {
+
+// Runs the named scenario ("streams", "fork", "fork_return", "fork_throw", "hold", "hold_return")
+// with the fail_at-th stand-in call after "begin" failing (0: none) and writes the call log, one
+// line per call, to out.  Returns its length, or -1 for an unknown scenario or a log over cap bytes.
+long hc_scope_scenario(const char* name, int fail_at, char* out, size_t cap) {
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!run_scenario(name, fail_at) || g_si.log.size() > cap) return -1;
+  std::memcpy(out, g_si.log.data(), g_si.log.size());
+  return (long)g_si.log.size();
 }
 
 }  // extern "C"

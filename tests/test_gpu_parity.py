@@ -1376,6 +1376,141 @@ def test_octet_final_exponentiation_knob(knob):
     assert r.returncode == 0 and "octet fe ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+# ------------------------- the context's streams and events: shutdown, and forks from two threads
+_SHUTDOWN_SCRIPT = r"""
+import json, os, sys
+root = sys.argv[1]
+sys.path[:0] = [root, os.path.join(root, "consensus-specs_amd")]
+import numpy as np
+from bls381_amd import _native as native
+gb = json.load(open(os.path.join(root, "tests", "golden", "bls_golden_batches.json")))
+items = [c for c in gb["verify"] if len(bytes.fromhex(c["message"])) == 32]
+vms = [c for c in gb["verify_multiple"] if len(c["pubkeys"]) == len(c["messages"])]
+off, pks, msgs, sigs, doms = [0], b"", b"", b"", b""
+for c in vms:
+    pks += b"".join(bytes.fromhex(p) for p in c["pubkeys"]); msgs += b"".join(bytes.fromhex(m) for m in c["messages"])
+    sigs += bytes.fromhex(c["signature"]); doms += int(c["domain"]).to_bytes(8, "big")
+    off.append(off[-1] + len(c["pubkeys"]))
+for rnd in range(2):
+    native.init(0)
+    got = native.verify_batch(b"".join(bytes.fromhex(c["pubkey"]) for c in items),
+                              b"".join(bytes.fromhex(c["message"]) for c in items),
+                              b"".join(bytes.fromhex(c["signature"]) for c in items),
+                              b"".join(int(c["domain"]).to_bytes(8, "big") for c in items))
+    assert list(got) == [c["expected"] for c in items], rnd
+    got = native.verify_multiple_batch(np.array(off, dtype=np.uint32), pks, msgs, 32, sigs, doms)
+    assert list(got) == [c["expected"] for c in vms], rnd
+    if rnd == 0:
+        native.lib().bls381_shutdown()
+print("shutdown ok")
+"""
+
+
+def test_shutdown_and_reinit():
+    """bls381_shutdown destroys the context's streams and events with everything else; a second
+    bls381_init builds them again.  In a child process (the suite's own context stays): the golden
+    32-byte-message verify cases as one verify_batch and the verify_multiple cases as one
+    verify_multiple_batch give the fixture verdicts before the shutdown and after the re-init."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _SHUTDOWN_SCRIPT, root], capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0 and "shutdown ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_forked_schedules_from_two_threads(native, golden, torsion):
+    """The four forked schedules of small batches, from two threads at once, each on a torch stream
+    and workspaces of its own, two rounds each: verify_batch_device of 5 items under the py_ecc
+    policy (decode_g1 on `side`, decode_g2 on `side2`) and inside subgroup_policy_scope("strict")
+    (both decodes on `side`), verify_multiple_batch_device of three calls (the task path: group sums
+    on `side`, signature decodes on `side2`) and verify_batch_randomized_device of 8 items in
+    sub-batches of 4 (the signature branch on `prio`).  One fork at a time holds the side streams,
+    so the threads' pipelines interleave between forks.  Inputs are tiled from the golden and
+    torsion fixtures at an offset per thread and round; verdicts == the fixtures' column for the
+    policy the call ran under."""
+    import ctypes
+    import threading
+    import torch
+    L = native.lib()
+    dev = torch.device("cuda", 0)
+    _, gb = golden
+    items = [(c, c["expected"], c["expected_strict"]) for c in gb["verify"] if len(bytes.fromhex(c["message"])) == 32]
+    items += [(c, c["expected_pyecc"], c["expected_strict"]) for c in torsion["verify"]]
+    vms = [(c, c["expected"]) for c in gb["verify_multiple"] if len(c["pubkeys"]) == len(c["messages"])]
+    vms += [(c, c["expected_pyecc"]) for c in torsion["verify_multiple"]]
+    t = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+
+    def verify_inputs(first, n):
+        sel = [items[(first + i) % len(items)] for i in range(n)]
+        d = [t(b"".join(bytes.fromhex(c["pubkey"]) for c, _, _ in sel)),
+             t(b"".join(bytes.fromhex(c["message"]) for c, _, _ in sel)),
+             t(b"".join(bytes.fromhex(c["signature"]) for c, _, _ in sel)),
+             t(b"".join(int(c["domain"]).to_bytes(8, "big") for c, _, _ in sel))]
+        return d, [int(e) for _, e, _ in sel], [int(e) for _, _, e in sel]
+
+    def vm_inputs(first):
+        sel = [vms[(first + i) % len(vms)] for i in range(3)]
+        off, pks, msgs, sigs, doms = [0], b"", b"", b"", b""
+        for c, _ in sel:
+            pks += b"".join(bytes.fromhex(p) for p in c["pubkeys"])
+            msgs += b"".join(bytes.fromhex(m) for m in c["messages"])
+            sigs += bytes.fromhex(c["signature"])
+            doms += int(c["domain"]).to_bytes(8, "big")
+            off.append(off[-1] + len(c["pubkeys"]))
+        return np.array(off, dtype=np.uint32), msgs, [t(pks or b"\0"), t(sigs), t(doms)], [int(e) for _, e in sel]
+
+    # everything a thread touches is made here, on the default stream, and complete before it starts
+    plans = []
+    for th in range(2):
+        rounds = []
+        for rnd in range(2):
+            first = 11 * th + 5 * rnd
+            v5, want_py, want_strict = verify_inputs(first, 5)
+            v8, want_rb, _ = verify_inputs(first + 2, 8)
+            rounds.append(dict(v5=v5, want_py=want_py, want_strict=want_strict, v8=v8, want_rb=want_rb,
+                               vm=vm_inputs(3 * th + rnd)))
+        nk = max(int(r["vm"][0][-1]) for r in rounds)
+        plans.append(dict(
+            rounds=rounds, stream=torch.cuda.Stream(dev),
+            ws5=torch.empty(L.bls381_verify_batch_workspace_size(5), dtype=torch.uint8, device=dev),
+            wsvm=torch.empty(L.bls381_verify_multiple_batch_workspace_size(3, nk, 32), dtype=torch.uint8, device=dev),
+            wsrb=torch.empty(L.bls381_verify_batch_randomized_workspace_size(8, 4), dtype=torch.uint8, device=dev),
+            out=[[torch.full((k,), 7, dtype=torch.uint8, device=dev) for k in (5, 5, 3, 8)] for _ in range(2)]))
+    torch.cuda.synchronize(dev)
+    errors = []
+
+    def work(p):
+        try:
+            s = ctypes.c_void_p(p["stream"].cuda_stream)
+            for r, out in zip(p["rounds"], p["out"]):
+                native.check(L.bls381_verify_batch_device(5, *[x.data_ptr() for x in r["v5"]], out[0].data_ptr(),
+                                                          p["ws5"].data_ptr(), s))
+                with native.subgroup_policy_scope("strict"):
+                    native.check(L.bls381_verify_batch_device(5, *[x.data_ptr() for x in r["v5"]], out[1].data_ptr(),
+                                                              p["ws5"].data_ptr(), s))
+                off, msgs, (d_pks, d_sigs, d_doms), _ = r["vm"]
+                native.check(L.bls381_verify_multiple_batch_device(
+                    3, off.ctypes.data_as(ctypes.c_void_p), msgs, 32, d_pks.data_ptr(), d_sigs.data_ptr(),
+                    d_doms.data_ptr(), out[2].data_ptr(), p["wsvm"].data_ptr(), s))
+                native.check(L.bls381_verify_batch_randomized_device(
+                    8, *[x.data_ptr() for x in r["v8"]], os.urandom(32), 4, out[3].data_ptr(), p["wsrb"].data_ptr(), s,
+                    None))
+            p["stream"].synchronize()
+        except Exception as e:   # noqa: BLE001 -- reported by the asserting thread
+            errors.append(repr(e))
+
+    native.set_subgroup_policy("pyecc")
+    threads = [threading.Thread(target=work, args=(p,)) for p in plans]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors
+    for p in plans:
+        for r, out in zip(p["rounds"], p["out"]):
+            got = [o.cpu().tolist() for o in out]
+            assert got == [r["want_py"], r["want_strict"], r["vm"][3], r["want_rb"]]
+
+
 # ------------------------------- full-size C3 epoch (VERDICT r04 next #6, SURVEY §8d C3)
 def test_c3_full_epoch_three_forms_agree(native):
     """The mainnet-preset epoch at full size: 1,024 committees x 128 members drawn from 8,192
