@@ -104,6 +104,24 @@ _SIGS = {
     "bls381_registry_process_deposits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p,
                                                                ctypes.c_uint64, _u8p, _u8p, ctypes.c_int, _u8p, _u8p,
                                                                ctypes.POINTER(ctypes.c_int64), _u8p, _u8p]),
+    "bls381_merkle_root_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32]),
+    "bls381_merkle_root": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
+                                          ctypes.c_uint64, _u8p]),
+    "bls381_merkle_root_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
+                                                 ctypes.c_uint64, _u8p, _u8p, _u8p]),
+    "bls381_merkle_proofs_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32]),
+    "bls381_merkle_proofs": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_size_t,
+                                            _u8p, _u8p, ctypes.c_size_t, _u8p]),
+    "bls381_merkle_proofs_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, ctypes.c_uint32,
+                                                   ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, _u8p, _u8p, _u8p]),
+    "bls381_ssz_list_root_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_ssz_list_root": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_size_t, _u8p, ctypes.c_uint32,
+                                            ctypes.c_int, _u8p]),
+    "bls381_ssz_list_root_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_size_t, ctypes.c_size_t, _u8p,
+                                                   ctypes.c_uint32, ctypes.c_int, _u8p, _u8p, _u8p]),
+    "bls381_deposits_build_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_deposits_build": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, _u8p, _u8p]),
+    "bls381_deposits_build_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),
     "bls381_shuffle_workspace_size": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]),
     "bls381_shuffle": (ctypes.c_int, [ctypes.c_uint64, _u8p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _u8p,
                                       _u8p]),

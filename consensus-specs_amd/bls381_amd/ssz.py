@@ -16,6 +16,12 @@ predefined below.
 ``verify_merkle_branch_batch`` runs the spec's verify_merkle_branch
 (0_beacon-chain.md:846-857) for a batch; the whole of process_deposit is
 ``registry.PubkeyRegistry.process_deposits``.
+
+Across items (csrc/bls381_merkle.hpp): ``merkle_root`` and ``merkle_proofs`` are the reference's
+utils/merkle_minimal.py trees (zero-padded to 2**depth leaves, the given ones from index
+``first``), ``build_deposits`` turns DepositData into Deposits with their proofs under one
+root.  ``hash_tree_root(typ, value)`` and ``signing_root(typ, value)`` take Python values of any
+type below, ``List(elem)`` and ``BYTES`` (the spec's ``bytes``) included.
 """
 from __future__ import annotations
 
@@ -44,8 +50,15 @@ def Vector(elem, n: int):
     return ("vector", elem, n)
 
 
+def List(elem):
+    return ("list", elem)
+
+
 def Container(*fields):
     return ("container", list(fields))
+
+
+BYTES = List(uint(1))      # the spec's `bytes`; values may be bytes objects
 
 
 # specs/core/0_beacon-chain.md containers whose roots are BLS messages
@@ -60,6 +73,31 @@ DepositData = Container(("pubkey", Bytes(48)), ("withdrawal_credentials", Bytes(
 Deposit = Container(("proof", Vector(Bytes(32), 32)), ("data", DepositData))
 BeaconBlockHeader = Container(("slot", uint(8)), ("parent_root", Bytes(32)), ("state_root", Bytes(32)),
                               ("body_root", Bytes(32)), ("signature", Bytes(96)))
+
+# further containers of 0_beacon-chain.md: the elements of BeaconState's and BeaconBlockBody's lists
+Fork = Container(("previous_version", Bytes(4)), ("current_version", Bytes(4)), ("epoch", uint(8)))
+Validator = Container(("pubkey", Bytes(48)), ("withdrawal_credentials", Bytes(32)),
+                      ("activation_eligibility_epoch", uint(8)), ("activation_epoch", uint(8)),
+                      ("exit_epoch", uint(8)), ("withdrawable_epoch", uint(8)), ("slashed", BOOL),
+                      ("effective_balance", uint(8)))
+Eth1Data = Container(("deposit_root", Bytes(32)), ("deposit_count", uint(8)), ("block_hash", Bytes(32)))
+ProposerSlashing = Container(("proposer_index", uint(8)), ("header_1", BeaconBlockHeader),
+                             ("header_2", BeaconBlockHeader))
+VoluntaryExit = Container(("epoch", uint(8)), ("validator_index", uint(8)), ("signature", Bytes(96)))
+Transfer = Container(("sender", uint(8)), ("recipient", uint(8)), ("amount", uint(8)), ("fee", uint(8)),
+                     ("slot", uint(8)), ("pubkey", Bytes(48)), ("signature", Bytes(96)))
+
+
+def is_fixed_size(typ) -> bool:
+    """ssz_impl.py:43-53."""
+    k = typ[0]
+    if k == "list":
+        return False
+    if k == "vector":
+        return is_fixed_size(typ[1])
+    if k == "container":
+        return all(is_fixed_size(t) for _, t in typ[1])
+    return True
 
 
 def item_size(typ) -> int:
@@ -199,3 +237,156 @@ def verify_merkle_branch_batch(leaves, proofs, depth: int, indices, root_or_root
         n, b"".join(leaves) or None, b"".join(flat) or None, depth, idx.ctypes.data_as(ctypes.c_void_p) if n else None,
         b"".join(roots) or None, 0 if single else 32, out.ctypes.data_as(ctypes.c_void_p) if n else None))
     return out.astype(bool)
+
+
+# ---------------------------------------------------------------- trees across items
+def _leaf_blob(leaves) -> bytes:
+    blob = bytes(leaves) if isinstance(leaves, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in leaves)
+    if len(blob) % 32:
+        raise ValueError("leaves are 32 bytes each")
+    return blob
+
+
+def chunk_depth(n: int) -> int:
+    """Depth of merkleize_chunks over n chunks (merkle_minimal.py): ceil(log2 n), 0 for n <= 1."""
+    return 0 if n <= 1 else (n - 1).bit_length()
+
+
+def merkle_root(leaves, depth: int, first: int = 0, length=None) -> bytes:
+    """Root of the tree with 2**depth leaves of which ``first .. first+n-1`` are ``leaves`` (32-byte
+    values, or their concatenation) and the others zero: get_merkle_root is depth 32,
+    merkleize_chunks depth ceil(log2 n).  No leaves give the zero node of ``depth``.  With
+    ``length`` the root is mixed with it (mix_in_length, ssz_impl.py:122-124)."""
+    blob = _leaf_blob(leaves)
+    out = ctypes.create_string_buffer(32)
+    _native.check(_native.lib().bls381_merkle_root(len(blob) // 32, blob or None, int(first), int(depth),
+                                                   0 if length is None else 1, 0 if length is None else int(length),
+                                                   out))
+    return out.raw
+
+
+def merkle_proofs(leaves, depth: int, indices, first: int = 0):
+    """get_merkle_proof of the same tree for each of ``indices`` (leaf indices below 2**depth; one
+    outside the window gets the proof of a zero leaf).  Returns (proofs, root): proofs[k] is the
+    concatenation of the ``depth`` siblings of indices[k], the form verify_merkle_branch_batch takes."""
+    blob = _leaf_blob(leaves)
+    depth = int(depth)
+    idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+    if any(int(i) >> depth for i in idx):
+        raise ValueError("merkle_proofs: an index at or above 2**depth")
+    row = 32 * depth
+    out = ctypes.create_string_buffer(max(row * len(idx), 1))
+    root = ctypes.create_string_buffer(32)
+    _native.check(_native.lib().bls381_merkle_proofs(len(blob) // 32, blob or None, int(first), depth, len(idx),
+                                                     idx.ctypes.data_as(ctypes.c_void_p) if len(idx) else None, out,
+                                                     row, root))
+    raw = out.raw
+    return [raw[row * k:row * k + row] for k in range(len(idx))], root.raw
+
+
+def build_deposits(deposit_datas, first_index: int = 0):
+    """Serialized Deposits (1,208 bytes: the proof, then the data) for serialized DepositData
+    (184 bytes each) that sit at leaves ``first_index ..`` of the deposit tree, and the tree's root:
+    what test/helpers/deposits.py of the reference builds with merkle_minimal.py, and what
+    ``PubkeyRegistry.process_deposits(deposits, first_index, root, ...)`` consumes."""
+    blob = b"".join(bytes(x) for x in deposit_datas)
+    n = len(blob) // 184
+    if n * 184 != len(blob):
+        raise ValueError("DepositData serializations are 184 bytes")
+    out = ctypes.create_string_buffer(max(1208 * n, 1))
+    root = ctypes.create_string_buffer(32)
+    _native.check(_native.lib().bls381_deposits_build(n, blob or None, int(first_index), out, root))
+    raw = out.raw
+    return [raw[1208 * i:1208 * i + 1208] for i in range(n)], root.raw
+
+
+SSZ_STACK = 64        # csrc/bls381_defs.hpp: chunks of a root program's stack
+SSZ_PROG_MAX = 512    # and its length in words
+
+
+def _program_fits(typ, signing: bool = False) -> bool:
+    """Whether one lane can run the type's root program (bls381_plan.hpp ssz_prog_ok's bounds)."""
+    if not is_fixed_size(typ):
+        return False
+    chunks = _peak_chunks(typ, signing)
+    return chunks is not None and len(compile_root(typ, signing)) <= SSZ_PROG_MAX
+
+
+def _peak_chunks(typ, signing: bool = False):
+    """The stack peak of the root program in chunks, or None above SSZ_STACK (found without
+    emitting the program of a large vector)."""
+    def peak(t, below):
+        # returns the peak while t's root is computed with `below` chunks under it, or None
+        k = t[0]
+        if k in ("uint", "bool"):
+            return below + 1
+        if k == "bytes" or (k == "vector" and t[1][0] in ("uint", "bool")):
+            pieces = max(1, (item_size(t) + 31) // 32)
+            return below + (1 << chunk_depth(pieces))
+        parts = [t[1]] * t[2] if k == "vector" else [ft for _, ft in t[1]]
+        if len(parts) + below > SSZ_STACK:
+            return None
+        top = below
+        for j, ft in enumerate(parts):
+            p = peak(ft, below + j)
+            if p is None:
+                return None
+            top = max(top, p)
+        return max(top, below + (1 << chunk_depth(len(parts))))
+    t = Container(*typ[1][:-1]) if signing else typ
+    p = peak(t, 0)
+    return p if p is not None and p <= SSZ_STACK else None
+
+
+def _series_root(typ, v) -> bytes:
+    """hash_tree_root of a list or vector (ssz_impl.py:143-155), by the element's kind."""
+    is_list = typ[0] == "list"
+    elem = typ[1]
+    n = len(v)
+    if typ[0] == "vector" and n != typ[2]:
+        raise ValueError("expected %d elements" % typ[2])
+    if elem[0] in ("uint", "bool"):
+        # packed (ssz_impl.py:110-119): the chunks of the serialization, zero-padded to 32 bytes
+        data = bytes(v) if isinstance(v, (bytes, bytearray)) and elem == uint(1) else b"".join(
+            serialize(elem, x) for x in v)
+        data += b"\x00" * (-len(data) % 32)
+        return merkle_root(data, chunk_depth(len(data) // 32), 0, n if is_list else None)
+    if _program_fits(elem):
+        # fixed-size composite elements: their roots, the tree and the length mix in one call
+        size = item_size(elem)
+        blob = b"".join(serialize(elem, x) for x in v)
+        prog = compile_root(elem)
+        out = ctypes.create_string_buffer(32)
+        _native.check(_native.lib().bls381_ssz_list_root(n, blob or None, size, prog.ctypes.data_as(ctypes.c_void_p),
+                                                         len(prog), 1 if is_list else 0, out))
+        return out.raw
+    # the slow path: variable-size elements (or ones too large for one lane), a call per element
+    roots = [hash_tree_root(elem, x) for x in v]
+    return merkle_root(roots, chunk_depth(n), 0, n if is_list else None)
+
+
+def hash_tree_root(typ, value) -> bytes:
+    """hash_tree_root of a Python value (ssz_impl.py:143-155).  A fixed-size type that fits one
+    lane's 64-chunk stack is one root program; a list or vector goes by its element -- fixed-size
+    composite: one bls381_ssz_list_root call; basic, and ``bytes``: one bls381_merkle_root over the
+    zero-padded serialization; variable-size: a root per element, then their tree (the slow path:
+    one call per element) -- and a container with such fields combines its field roots through
+    merkle_root."""
+    if _program_fits(typ):
+        return hash_tree_root_batch(typ, [serialize(typ, value)])[0]
+    if typ[0] in ("list", "vector"):
+        return _series_root(typ, value)
+    if typ[0] == "bytes":      # a BytesN of more than 64 chunks
+        return _series_root(Vector(uint(1), typ[1]), bytes(value))
+    roots = [hash_tree_root(t, value[name]) for name, t in typ[1]]
+    return merkle_root(roots, chunk_depth(len(roots)))
+
+
+def signing_root(typ, value) -> bytes:
+    """signing_root of a Python container value (ssz_impl.py:158-163): the last field left out."""
+    if typ[0] != "container" or len(typ[1]) < 2:
+        raise ValueError("signing_root needs a container with at least two fields")
+    if _program_fits(typ, True):
+        return signing_root_batch(typ, [serialize(typ, value)])[0]
+    roots = [hash_tree_root(t, value[name]) for name, t in typ[1][:-1]]
+    return merkle_root(roots, chunk_depth(len(roots)))

@@ -56,6 +56,7 @@ struct Ctx {
   size_t ws_cap = 0;
   std::mutex mu;
   KeepList keep;
+  uint8_t* ztab = nullptr;   // the zero nodes Z[0 .. 64] of the Merkle trees (bls381_merkle.hpp), made with the context
   ~Ctx() { streams_destroy(q); }
 };
 // the SIMD count of the device this thread's last get_ctx selected (256 CUs until then)
@@ -109,6 +110,15 @@ Ctx* get_ctx(int* rc) {
     c->device = dev;
     c->simds = (size_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * 4;
     if (streams_create(c->q) != hipSuccess) { t_err = "stream create failed"; *rc = BLS381_EHIP; return nullptr; }
+    uint8_t zeros[MERKLE_ZERO_TABLE_BYTES];
+    merkle_zero_table(zeros);
+    if (hipMalloc(&c->ztab, sizeof(zeros)) != hipSuccess ||
+        hipMemcpy(c->ztab, zeros, sizeof(zeros), hipMemcpyHostToDevice) != hipSuccess) {
+      if (c->ztab) (void)hipFree(c->ztab);
+      t_err = "zero-node table failed";
+      *rc = BLS381_EHIP;
+      return nullptr;
+    }
     g_ctx[dev] = c.release();
   }
   if (hipSetDevice(dev) != hipSuccess) { t_err = "hipSetDevice failed"; *rc = BLS381_ENODEV; return nullptr; }
@@ -815,6 +825,7 @@ void bls381_shutdown(void) {
     (void)hipDeviceSynchronize();
     keep_clear(c->keep);
     if (c->ws) (void)hipFree(c->ws);
+    if (c->ztab) (void)hipFree(c->ztab);
     delete c;
   }
   g_ctx.clear();
@@ -1772,6 +1783,265 @@ int bls381_merkle_branch_batch(size_t n, const uint8_t* leaves32, const uint8_t*
     TRY(hc.upload(d_roots, roots32, root_bytes));
     TRY(bls381_merkle_branch_batch_device(n, d_leaves, d_proofs, depth, d_idx, d_roots, root_stride, d_ok, hc.s));
     TRY(hc.download(ok_out, d_ok, n));
+    return hc.finish();
+  });
+}
+
+// ---- Merkle trees across items: roots, proofs, list roots, the deposits builder
+// (the plan, the level table and the workspace carve: bls381_plan.hpp)
+// Queues the tree of `p` over d_leaves: the passes, then the last step, which writes d_root.
+static int merkle_tree_impl(Ctx* c, const MerklePlan& p, const uint8_t* d_leaves, const MerkleWs& w, int mix,
+                            uint64_t length, uint8_t* d_root, hipStream_t s) {
+  Held<std::vector<merkle_level>> lv(c->keep, s, std::vector<merkle_level>(p.lv, p.lv + MERKLE_DEPTH_MAX + 1));
+  HIPC(hipMemcpyAsync(w.lv, lv->data(), sizeof(p.lv), hipMemcpyHostToDevice, s));
+  auto row = [&](uint32_t h) -> const uint8_t* { return h == 0 ? d_leaves : w.nodes + p.lv[h].off; };
+  for (const merkle_pass& ps : p.passes)
+    LAUNCH("merkle_reduce", s, dim3((unsigned)ps.tiles), dim3(MERKLE_TILE / 2), k_merkle_reduce, row(ps.h0), w.nodes,
+           (const merkle_level*)w.lv, (const uint8_t*)c->ztab, ps.h0, ps.steps, ps.tile0);
+  LAUNCH("merkle_finish", s, dim3(1), dim3(64), k_merkle_finish, p.n ? row(p.top) : (const uint8_t*)nullptr, w.nodes,
+         (const merkle_level*)w.lv, (const uint8_t*)c->ztab, p.top, p.depth, p.first, mix, length, d_root);
+  return 0;
+}
+static int merkle_proofs_impl(Ctx* c, const MerklePlan& p, const uint8_t* d_leaves, const MerkleWs& w, size_t n_idx,
+                              const uint64_t* d_indices, uint64_t index_base, uint8_t* d_proofs, size_t stride,
+                              hipStream_t s) {
+  LAUNCH("merkle_proofs", s, dim3(grid_for(n_idx * p.depth)), dim3(KBLOCK), k_merkle_proofs, n_idx, d_indices,
+         index_base, p.depth, d_leaves, (const uint8_t*)w.nodes, (const merkle_level*)w.lv, (const uint8_t*)c->ztab,
+         d_proofs, stride);
+  return 0;
+}
+static bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+size_t bls381_merkle_root_workspace_size(size_t n, uint64_t first, uint32_t depth) {
+  return merkle_args_in_range(n, first, depth) ? merkle_ws_size(n, first, depth, false) : 0;
+}
+size_t bls381_merkle_proofs_workspace_size(size_t n, uint64_t first, uint32_t depth) {
+  return merkle_args_in_range(n, first, depth) ? merkle_ws_size(n, first, depth, true) : 0;
+}
+
+int bls381_merkle_root_device(size_t n, const uint8_t* d_leaves32, uint64_t first, uint32_t depth, int mix_length,
+                              uint64_t length, uint8_t* d_root32, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!merkle_args_in_range(n, first, depth) || !d_root32 || !d_workspace || (n && !d_leaves32) ||
+        !aligned4(d_leaves32))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    const MerklePlan p = plan_merkle(n, first, depth, false);
+    Bump b(d_workspace, bls381_merkle_root_workspace_size(n, first, depth));
+    const MerkleWs w = carve_merkle(b, p.node_bytes);
+    return merkle_tree_impl(c, p, d_leaves32, w, mix_length, length, d_root32, (hipStream_t)stream);
+  });
+}
+
+int bls381_merkle_root(size_t n, const uint8_t* leaves32, uint64_t first, uint32_t depth, int mix_length,
+                       uint64_t length, uint8_t root[32]) {
+  return guarded([&]() -> int {
+    if (!merkle_args_in_range(n, first, depth) || !root || (n && !leaves32)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_merkle_root_workspace_size(n, first, depth);
+    uint8_t *d_leaves, *d_root, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_leaves = b.take<uint8_t>(32 * n);
+      d_root = b.take<uint8_t>(32);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_leaves, leaves32, 32 * n));
+    TRY(bls381_merkle_root_device(n, d_leaves, first, depth, mix_length, length, d_root, d_ws, hc.s));
+    TRY(hc.download(root, d_root, 32));
+    return hc.finish();
+  });
+}
+
+static bool merkle_proofs_args_ok(size_t n, const void* leaves, uint64_t first, uint32_t depth, size_t n_idx,
+                                  const void* indices, const void* proofs, size_t proof_stride, const void* root) {
+  if (!merkle_args_in_range(n, first, depth) || n_idx > (size_t)INT32_MAX || proof_stride < (size_t)32 * depth)
+    return false;
+  return root && (n == 0 || leaves) && (n_idx == 0 || (indices && (proofs || depth == 0)));
+}
+
+int bls381_merkle_proofs_device(size_t n, const uint8_t* d_leaves32, uint64_t first, uint32_t depth, size_t n_idx,
+                                const uint64_t* d_indices, uint8_t* d_proofs, size_t proof_stride, uint8_t* d_root32,
+                                void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!merkle_proofs_args_ok(n, d_leaves32, first, depth, n_idx, d_indices, d_proofs, proof_stride, d_root32) ||
+        !d_workspace || !aligned4(d_leaves32) || !aligned4(d_proofs) || (proof_stride & 3) ||
+        ((uintptr_t)d_indices & 7))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MerklePlan p = plan_merkle(n, first, depth, true);
+    Bump b(d_workspace, bls381_merkle_proofs_workspace_size(n, first, depth));
+    const MerkleWs w = carve_merkle(b, p.node_bytes);
+    TRY(merkle_tree_impl(c, p, d_leaves32, w, 0, 0, d_root32, s));
+    return merkle_proofs_impl(c, p, d_leaves32, w, n_idx, d_indices, 0, d_proofs, proof_stride, s);
+  });
+}
+
+int bls381_merkle_proofs(size_t n, const uint8_t* leaves32, uint64_t first, uint32_t depth, size_t n_idx,
+                         const uint64_t* indices, uint8_t* proofs, size_t proof_stride, uint8_t root[32]) {
+  return guarded([&]() -> int {
+    if (!merkle_proofs_args_ok(n, leaves32, first, depth, n_idx, indices, proofs, proof_stride, root))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_merkle_proofs_workspace_size(n, first, depth), row = (size_t)32 * depth;
+    uint8_t *d_leaves, *d_proofs, *d_root, *d_ws;
+    uint64_t* d_idx;
+    TRY(hc.carve([&](Bump& b) {
+      d_leaves = b.take<uint8_t>(32 * n);
+      d_idx = b.take<uint64_t>(n_idx);
+      d_proofs = b.take<uint8_t>(row * n_idx);
+      d_root = b.take<uint8_t>(32);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_leaves, leaves32, 32 * n));
+    TRY(hc.upload(d_idx, indices, 8 * n_idx));
+    TRY(bls381_merkle_proofs_device(n, d_leaves, first, depth, n_idx, d_idx, d_proofs, row, d_root, d_ws, hc.s));
+    // packed on the device; the caller's rows are proof_stride apart and only their proofs are written
+    if (row && n_idx)
+      HIPC(hipMemcpy2DAsync(proofs, proof_stride, d_proofs, row, row, n_idx, hipMemcpyDeviceToHost, hc.s));
+    TRY(hc.download(root, d_root, 32));
+    return hc.finish();
+  });
+}
+
+// hash_tree_root of a List / Vector of n fixed-size composite elements: the elements' roots, the
+// tree of depth ceil(log2 n) over them, mix_in_length(n) for a list
+struct ListRootWs {
+  uint8_t* roots;
+  SszWs ssz;
+  MerkleWs merkle;
+};
+static ListRootWs carve_list_root(Bump& b, const MerklePlan& p) {
+  ListRootWs w;
+  w.roots = b.take<uint8_t>(32 * (size_t)p.n);
+  w.ssz = carve_ssz(b);
+  w.merkle = carve_merkle(b, p.node_bytes);
+  return w;
+}
+size_t bls381_ssz_list_root_workspace_size(size_t n) {
+  if (n > (size_t)INT32_MAX) return 0;
+  const MerklePlan p = plan_merkle(n, 0, merkle_chunk_depth(n), false);
+  return carved_bytes([&](Bump& b) { carve_list_root(b, p); });
+}
+
+int bls381_ssz_list_root_device(size_t n, const uint8_t* d_items, size_t stride, size_t item_size,
+                                const uint32_t* h_prog, uint32_t prog_len, int mix_length, uint8_t* d_root32,
+                                void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (n > (size_t)INT32_MAX || !d_root32 || !d_workspace || (n && !d_items) || item_size == 0 ||
+        stride < item_size || !ssz_prog_ok(h_prog, prog_len, item_size))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MerklePlan p = plan_merkle(n, 0, merkle_chunk_depth(n), false);
+    Bump b(d_workspace, bls381_ssz_list_root_workspace_size(n));
+    const ListRootWs w = carve_list_root(b, p);
+    if (n) TRY(ssz_root_impl(n, d_items, stride, h_prog, prog_len, w.roots, w.ssz, s, c));
+    return merkle_tree_impl(c, p, w.roots, w.merkle, mix_length, n, d_root32, s);
+  });
+}
+
+int bls381_ssz_list_root(size_t n, const uint8_t* items, size_t item_size, const uint32_t* prog, uint32_t prog_len,
+                         int mix_length, uint8_t root[32]) {
+  return guarded([&]() -> int {
+    if (n > (size_t)INT32_MAX || !root || (n && !items) || item_size == 0 || !ssz_prog_ok(prog, prog_len, item_size))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_ssz_list_root_workspace_size(n);
+    uint8_t *d_items, *d_root, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_items = b.take<uint8_t>(n * item_size);
+      d_root = b.take<uint8_t>(32);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_items, items, n * item_size));
+    TRY(bls381_ssz_list_root_device(n, d_items, item_size, item_size, prog, prog_len, mix_length, d_root, d_ws, hc.s));
+    TRY(hc.download(root, d_root, 32));
+    return hc.finish();
+  });
+}
+
+// n DepositData -> n Deposits under one root: the leaves hash_tree_root(data), the depth-32 tree
+// with every level kept, each leaf's proof written into its Deposit, the data copied behind it
+struct DepositsBuildWs {
+  uint8_t* leaves;
+  SszWs ssz;
+  MerkleWs merkle;
+};
+// (the rows' sizes depend on first_index, by at most one node per level: merkle_node_bound)
+static DepositsBuildWs carve_deposits_build(Bump& b, size_t n) {
+  DepositsBuildWs w;
+  w.leaves = b.take<uint8_t>(32 * n);
+  w.ssz = carve_ssz(b);
+  w.merkle = carve_merkle(b, merkle_node_bound(n, DEPOSIT_PROOF_DEPTH));
+  return w;
+}
+size_t bls381_deposits_build_workspace_size(size_t n) {
+  if (n > (size_t)INT32_MAX) return 0;
+  return carved_bytes([&](Bump& b) { carve_deposits_build(b, n); });
+}
+
+int bls381_deposits_build_device(size_t n, const uint8_t* d_deposit_data, uint64_t first_index, uint8_t* d_deposits,
+                                 uint8_t* d_deposit_root32, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!merkle_args_in_range(n, first_index, DEPOSIT_PROOF_DEPTH) || !d_deposit_root32 || !d_workspace ||
+        (n && (!d_deposit_data || !d_deposits)) || !aligned4(d_deposits))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MerklePlan p = plan_merkle(n, first_index, DEPOSIT_PROOF_DEPTH, true);
+    Bump b(d_workspace, bls381_deposits_build_workspace_size(n));
+    const DepositsBuildWs w = carve_deposits_build(b, n);
+    if (n)
+      TRY(ssz_root_impl(n, d_deposit_data, DEPOSIT_DATA_BYTES, DEPOSIT_ROOT_PROG, DEPOSIT_ROOT_PROG_LEN, w.leaves,
+                        w.ssz, s, c));
+    TRY(merkle_tree_impl(c, p, w.leaves, w.merkle, 0, 0, d_deposit_root32, s));
+    TRY(merkle_proofs_impl(c, p, w.leaves, w.merkle, n, nullptr, first_index, d_deposits, DEPOSIT_BYTES, s));
+    LAUNCH("deposit_data_copy", s, dim3(grid_for(DEPOSIT_DATA_BYTES * n)), dim3(KBLOCK), k_scatter_field, n,
+           d_deposit_data, (uint32_t)DEPOSIT_DATA_BYTES, d_deposits, DEPOSIT_BYTES, (uint32_t)DEPOSIT_PROOF_BYTES);
+    return 0;
+  });
+}
+
+int bls381_deposits_build(size_t n, const uint8_t* deposit_data, uint64_t first_index, uint8_t* deposits,
+                          uint8_t deposit_root[32]) {
+  return guarded([&]() -> int {
+    if (!merkle_args_in_range(n, first_index, DEPOSIT_PROOF_DEPTH) || !deposit_root ||
+        (n && (!deposit_data || !deposits)))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_deposits_build_workspace_size(n);
+    uint8_t *d_data, *d_dep, *d_root, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_data = b.take<uint8_t>(DEPOSIT_DATA_BYTES * n);
+      d_dep = b.take<uint8_t>(DEPOSIT_BYTES * n);
+      d_root = b.take<uint8_t>(32);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_data, deposit_data, DEPOSIT_DATA_BYTES * n));
+    TRY(bls381_deposits_build_device(n, d_data, first_index, d_dep, d_root, d_ws, hc.s));
+    TRY(hc.download(deposits, d_dep, DEPOSIT_BYTES * n));
+    TRY(hc.download(deposit_root, d_root, 32));
     return hc.finish();
   });
 }

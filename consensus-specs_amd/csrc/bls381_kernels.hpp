@@ -12,6 +12,7 @@
 #include "bls381_pair.hpp"
 #include "bls381_quad.hpp"
 #include "bls381_ssz.hpp"
+#include "bls381_merkle.hpp"
 #include "bls381_shuffle.hpp"
 
 namespace bls381 {
@@ -1536,6 +1537,111 @@ __global__ void __launch_bounds__(KBLOCK) k_merkle_branch(size_t n, const uint8_
   for (int w = 0; w < 8; ++w) d |= v[w] ^ g_be32(root + 4 * w);
   ok[i] = d == 0;
   if (d != 0 && first_bad) atomicMin(first_bad, (uint32_t)i);
+}
+
+// ------------------------------------------------- Merkle trees across items --
+// (the node rules, the tile's LDS layout: bls381_merkle.hpp; levels and passes: bls381_plan.hpp)
+typedef __attribute__((address_space(1))) const merkle_level g_clevel;
+
+// One pass of the tree reduction: workgroup b takes tile tile0 + b of level h0 -- MERKLE_TILE
+// nodes, aligned to MERKLE_TILE in absolute node index -- `steps` levels up.  Each lane hashes
+// one pair read from `in` (the row of level h0: its real nodes, 32 bytes each; a node outside
+// them is Z[h0] from ztab), then the tile is halved in LDS.  Node j of level h0 + s is written
+// to its row of `nodes` when the level table says the level is kept and the node real; a
+// virtual node's value is Z of its level, by hashing, and is written nowhere.
+__global__ void __launch_bounds__(MERKLE_TILE / 2) k_merkle_reduce(const uint8_t* __restrict__ in, uint8_t* nodes,
+                                                                  const merkle_level* __restrict__ lv,
+                                                                  const uint8_t* __restrict__ ztab, uint32_t h0,
+                                                                  uint32_t steps, uint64_t tile0) {
+  constexpr uint32_t T = MERKLE_TILE / 2;
+  __shared__ uint32_t tile[2][8][MERKLE_LDS_ROW];
+  const uint32_t l = threadIdx.x;
+  const uint64_t t = tile0 + blockIdx.x;
+  g_clevel* L = (g_clevel*)lv;
+  g_u32* out = (g_u32*)nodes;
+  uint64_t j = t * T + l;
+  uint32_t v[8];
+  merkle_first_step(v, (g_cu32*)in, L[h0].base, L[h0].count, j, (g_cu32*)(ztab + 32 * h0));
+  bool live = true;
+  uint32_t p = 0;
+  for (uint32_t s = 1;; ++s) {
+    // v: node j of level h0 + s, in the lanes that are live
+    if (live) merkle_keep(out, L[h0 + s].base, L[h0 + s].count, L[h0 + s].off, j, v);
+    if (s == steps) break;
+    if (live)
+      for (int w = 0; w < 8; ++w) tile[p][w][merkle_lds_slot(l)] = v[w];
+    __syncthreads();   // the next step writes the other buffer: one barrier per step
+    live = l < (T >> s);
+    if (live) {
+      uint32_t a[8], b[8];
+      for (int w = 0; w < 8; ++w) {
+        a[w] = tile[p][w][merkle_lds_slot(2 * l)];
+        b[w] = tile[p][w][merkle_lds_slot(2 * l + 1)];
+      }
+      sha256_pair(v, a, b);
+    }
+    j = ((t * T) >> s) + l;
+    p ^= 1;
+  }
+}
+
+// The last step, one lane: the single real node of level `top` (node: its 32 bytes, or null for
+// an empty tree, whose root is Z[depth]) folded with Z[g] up to `depth`, each level kept when the
+// table says so; then the optional mix_in_length; the 32 bytes of the root.
+__global__ void __launch_bounds__(64) k_merkle_finish(const uint8_t* __restrict__ node, uint8_t* nodes,
+                                                      const merkle_level* __restrict__ lv,
+                                                      const uint8_t* __restrict__ ztab, uint32_t top, uint32_t depth,
+                                                      uint64_t first, int mix, uint64_t length,
+                                                      uint8_t* __restrict__ root) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  g_clevel* L = (g_clevel*)lv;
+  g_cu32* Z = (g_cu32*)ztab;
+  uint32_t v[8];
+  if (node) {
+    merkle_load(v, (g_cu32*)node);
+    for (uint32_t g = top; g < depth; ++g) {
+      merkle_fold_step(v, first, g, Z);
+      merkle_keep((g_u32*)nodes, L[g + 1].base, L[g + 1].count, L[g + 1].off, L[g + 1].base, v);
+    }
+  } else {
+    merkle_load(v, Z + 8 * depth);
+  }
+  if (mix) merkle_mix_in_length(v, length);
+  for (int w = 0; w < 8; ++w)
+    for (int b = 0; b < 4; ++b) root[4 * w + b] = (uint8_t)(v[w] >> (24 - 8 * b));
+}
+
+// get_merkle_proof for n_idx leaf indices (indices[k], or index_base + k when indices is null):
+// one lane per sibling.  Sibling h of index i is node (h, (i >> h) ^ 1) of the kept levels (level
+// 0: the leaves), or Z[h]; it goes to proofs + k proof_stride + 32 h (4-byte aligned).
+__global__ void __launch_bounds__(KBLOCK) k_merkle_proofs(size_t n_idx, const uint64_t* __restrict__ indices,
+                                                          uint64_t index_base, uint32_t depth,
+                                                          const uint8_t* __restrict__ leaves,
+                                                          const uint8_t* __restrict__ nodes,
+                                                          const merkle_level* __restrict__ lv,
+                                                          const uint8_t* __restrict__ ztab,
+                                                          uint8_t* __restrict__ proofs, size_t proof_stride) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_idx * depth) return;
+  const size_t k = t / depth;
+  const uint32_t h = (uint32_t)(t % depth);   // h < depth <= 64
+  const uint64_t i = indices ? indices[k] : index_base + k;
+  g_clevel* L = (g_clevel*)lv;
+  const uint64_t off = L[h].off;
+  const bool kept = h == 0 || off != MERKLE_NONE;
+  g_cu32* row = h == 0 ? (g_cu32*)leaves : (g_cu32*)(nodes + (kept ? off : 0));
+  g_cu32* src = merkle_node_src(row, L[h].base, kept ? L[h].count : 0, (i >> h) ^ 1, (g_cu32*)(ztab + 32 * h));
+  g_u32* dst = (g_u32*)(proofs + k * proof_stride + 32 * h);
+  for (int w = 0; w < 8; ++w) dst[w] = src[w];
+}
+
+// the reverse of k_gather_field: packed fields of len bytes into [off, off + len) of n strided items
+__global__ void __launch_bounds__(KBLOCK) k_scatter_field(size_t n, const uint8_t* __restrict__ in, uint32_t len,
+                                                          uint8_t* __restrict__ items, size_t stride, uint32_t off) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * len) return;
+  const size_t i = t / len, b = t % len;
+  items[i * stride + off + b] = in[t];
 }
 
 // outcomes of process_deposit (include/bls381.h BLS381_DEPOSIT_*)

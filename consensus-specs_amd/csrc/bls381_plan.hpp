@@ -1,6 +1,7 @@
 // Host-side planning of the launch pipelines in bls381_capi.hip: workspace carving, chunk
 // plans for the aggregation trees and the segmented Fp12 products, the verify_multiple
-// grouping (py_ecc's semantics) and the workspace bounds.  Pure host C++ -- no HIP call,
+// grouping (py_ecc's semantics), the levels and passes of the Merkle trees across items, and
+// the workspace bounds.  Pure host C++ -- no HIP call,
 // no device code -- so the unit-test build (host_check.cpp) compiles it with g++ and
 // tests/test_host_plan.py reaches it without a GPU.
 #pragma once
@@ -508,6 +509,100 @@ inline size_t deposit_table_slots(size_t n) {
   size_t t = 16;
   while (t < 2 * n) t <<= 1;
   return t;
+}
+
+// ----------------------------------------------------------- Merkle trees --
+// The plan of tree(leaves[0..n), first, depth) (bls381_merkle.hpp): the tree with 2^depth leaves
+// of which first .. first+n-1 are given and every other one is the zero chunk.  Level h has real
+// nodes [first >> h, (first+n-1) >> h]; a pass of k_merkle_reduce takes tiles of MERKLE_TILE
+// nodes of one level, aligned in absolute node index, up MERKLE_TILE_LOG levels (or to `depth`),
+// and passes repeat until one real node is left at level `top`; one lane folds that node with
+// zero nodes up to `depth`.  Kept rows lie back to back in one slice of the workspace, row h
+// starting at node first >> h: every level 1 .. depth with keep (the proofs' source), else only
+// the levels a pass ends on (the next pass's input).
+constexpr uint32_t MERKLE_TILE_LOG = 8;
+constexpr uint32_t MERKLE_TILE = 1u << MERKLE_TILE_LOG;   // W: nodes of a tile, two per lane
+constexpr uint32_t MERKLE_DEPTH_MAX = 64;
+constexpr uint64_t MERKLE_NONE = UINT64_MAX;
+// real nodes [base, base + count) of a level; off: the row's byte offset in the node slice, or
+// MERKLE_NONE when the level is not kept (level 0 is the caller's leaves)
+struct merkle_level {
+  uint64_t base, count, off;
+};
+struct merkle_pass {
+  uint32_t h0, steps;     // input level, levels climbed
+  uint64_t tile0, tiles;  // absolute index of the first tile, tile count (= workgroups)
+};
+struct MerklePlan {
+  uint64_t n = 0, first = 0;
+  uint32_t depth = 0, top = 0;   // top: the level the passes end on, with one real node
+  merkle_level lv[MERKLE_DEPTH_MAX + 1];
+  std::vector<merkle_pass> passes;
+  size_t node_bytes = 0;
+};
+inline uint64_t merkle_shr(uint64_t x, uint32_t h) { return h >= 64 ? 0 : x >> h; }
+// the tree's shape: depth <= 64, first + n neither overflowing nor above 2^depth
+inline bool merkle_shape_ok(uint64_t n, uint64_t first, uint32_t depth) {
+  if (depth > MERKLE_DEPTH_MAX || first + n < first) return false;
+  return depth == 64 || first + n <= (uint64_t)1 << depth;
+}
+// what the entry points take: the shape, and at most 2^31 - 1 leaves
+inline bool merkle_args_in_range(uint64_t n, uint64_t first, uint32_t depth) {
+  return merkle_shape_ok(n, first, depth) && n <= (uint64_t)INT32_MAX;
+}
+inline MerklePlan plan_merkle(uint64_t n, uint64_t first, uint32_t depth, bool keep) {
+  if (!merkle_shape_ok(n, first, depth)) throw std::invalid_argument("merkle tree shape");
+  MerklePlan p;
+  p.n = n; p.first = first; p.depth = depth;
+  for (uint32_t h = 0; h <= MERKLE_DEPTH_MAX; ++h) {
+    const uint64_t base = merkle_shr(first, h);
+    p.lv[h] = {base, n && h <= depth ? merkle_shr(first + n - 1, h) - base + 1 : 0, MERKLE_NONE};
+  }
+  uint32_t h = 0;
+  while (n && h < depth && p.lv[h].count > 1) {
+    const uint32_t steps = std::min(MERKLE_TILE_LOG, depth - h);
+    const uint64_t tile0 = p.lv[h].base / MERKLE_TILE;
+    p.passes.push_back({h, steps, tile0, (p.lv[h].base + p.lv[h].count - 1) / MERKLE_TILE - tile0 + 1});
+    h += steps;
+    if (!keep) p.lv[h].off = 0;   // marked; offsets below
+  }
+  p.top = h;
+  size_t off = 0;
+  for (uint32_t g = 1; g <= depth; ++g) {
+    if (!(keep ? n != 0 : p.lv[g].off == 0)) continue;
+    p.lv[g].off = off;
+    off += 32 * (size_t)p.lv[g].count;
+  }
+  p.node_bytes = off;
+  return p;
+}
+// the device copy of the level table, then the node slice
+struct MerkleWs {
+  merkle_level* lv;
+  uint8_t* nodes;
+};
+inline MerkleWs carve_merkle(Bump& b, size_t node_bytes) {
+  MerkleWs w;
+  w.lv = b.take<merkle_level>(MERKLE_DEPTH_MAX + 1);
+  w.nodes = b.take<uint8_t>(node_bytes);
+  return w;
+}
+inline size_t merkle_ws_size(uint64_t n, uint64_t first, uint32_t depth, bool keep) {
+  const MerklePlan p = plan_merkle(n, first, depth, keep);
+  return carved_bytes([&](Bump& b) { carve_merkle(b, p.node_bytes); });
+}
+// the kept rows of n leaves wherever the window starts: level h has at most ((n-1) >> h) + 2 real
+// nodes (a caller that sizes its workspace before the first index is known: the deposits builder)
+inline size_t merkle_node_bound(uint64_t n, uint32_t depth) {
+  size_t s = 0;
+  for (uint32_t h = 1; n && h <= depth; ++h) s += 32 * (size_t)(merkle_shr(n - 1, h) + 2);
+  return s;
+}
+// depth of merkleize_chunks over n chunks (merkle_minimal.py): ceil(log2 n), 0 for n <= 1
+inline uint32_t merkle_chunk_depth(uint64_t n) {
+  uint32_t d = 0;
+  while (d < 64 && ((uint64_t)1 << d) < n) ++d;
+  return d;
 }
 
 }  // namespace bls381

@@ -22,6 +22,7 @@
 #include "bls381_plan.hpp"
 #include "bls381_shuffle.hpp"
 #include "bls381_ssz.hpp"
+#include "bls381_merkle.hpp"
 
 // ---- stand-ins for the HIP types and runtime calls that bls381_scope.hpp is written against.
 // Every call appends one line to a log (hc_scope_scenario, at the end of this file, returns it);
@@ -530,6 +531,180 @@ int hc_merkle_branch(const uint8_t* leaf32, const uint8_t* proof, uint32_t depth
   for (int w = 0; w < 8; ++w)
     for (int b = 0; b < 4; ++b) d |= (uint32_t)((uint8_t)(v[w] >> (24 - 8 * b)) ^ root32[4 * w + b]);
   return d == 0;
+}
+
+// ---- Merkle trees across items (bls381_merkle.hpp, the plan of bls381_plan.hpp): what the
+// kernels k_merkle_reduce / k_merkle_finish / k_merkle_proofs run, the workgroups and lanes as
+// plain loops, tiles dealt to `threads` host threads.
+uint32_t hc_merkle_tile(void) { return MERKLE_TILE; }
+
+namespace {
+struct HcTree {
+  MerklePlan p;
+  std::vector<uint32_t> leaves, nodes, ztab;
+  const uint32_t* row(uint32_t h) const { return h == 0 ? leaves.data() : nodes.data() + p.lv[h].off / 4; }
+};
+
+// one workgroup of k_merkle_reduce: tile t of pass ps
+void hc_merkle_tile_run(HcTree& tr, const merkle_pass& ps, uint64_t t) {
+  constexpr uint32_t T = MERKLE_TILE / 2;
+  static thread_local uint32_t tile[2][8][MERKLE_LDS_ROW];
+  const merkle_level* L = tr.p.lv;
+  uint32_t v[T][8];
+  for (uint32_t l = 0; l < T; ++l) {
+    const uint64_t j = t * T + l;
+    merkle_first_step(v[l], tr.row(ps.h0), L[ps.h0].base, L[ps.h0].count, j,
+                      (const uint32_t*)tr.ztab.data() + 8 * ps.h0);
+  }
+  uint32_t p = 0, live = T;
+  for (uint32_t s = 1;; ++s) {
+    const merkle_level& o = L[ps.h0 + s];
+    for (uint32_t l = 0; l < live; ++l)
+      merkle_keep(tr.nodes.data(), o.base, o.count, o.off, ((t * T) >> (s - 1)) + l, v[l]);
+    if (s == ps.steps) break;
+    for (uint32_t l = 0; l < live; ++l)
+      for (int w = 0; w < 8; ++w) tile[p][w][merkle_lds_slot(l)] = v[l][w];
+    live = T >> s;
+    for (uint32_t l = 0; l < live; ++l) {
+      uint32_t a[8], b[8];
+      for (int w = 0; w < 8; ++w) {
+        a[w] = tile[p][w][merkle_lds_slot(2 * l)];
+        b[w] = tile[p][w][merkle_lds_slot(2 * l + 1)];
+      }
+      sha256_pair(v[l], a, b);
+    }
+    p ^= 1;
+  }
+}
+
+// the whole tree: the passes, then k_merkle_finish's fold, mix and root
+void hc_merkle_tree(HcTree& tr, const uint8_t* leaves32, int mix, uint64_t length, int threads, uint8_t* root32) {
+  const MerklePlan& p = tr.p;
+  // exact sizes, so that the sanitized build sees any access outside a row
+  tr.leaves.assign(8 * (size_t)p.n, 0);
+  if (p.n) std::memcpy(tr.leaves.data(), leaves32, 32 * (size_t)p.n);
+  tr.nodes.assign(p.node_bytes / 4, 0xEEEEEEEEu);
+  uint8_t z[MERKLE_ZERO_TABLE_BYTES];
+  merkle_zero_table(z);
+  tr.ztab.assign(MERKLE_ZERO_TABLE_BYTES / 4, 0);
+  std::memcpy(tr.ztab.data(), z, sizeof(z));
+  if (threads < 1) threads = 1;
+  for (const merkle_pass& ps : p.passes) {
+    std::vector<std::thread> pool;
+    for (int k = 0; k < threads; ++k)
+      pool.emplace_back([&tr, &ps, k, threads] {
+        for (uint64_t b = (uint64_t)k; b < ps.tiles; b += (uint64_t)threads) hc_merkle_tile_run(tr, ps, ps.tile0 + b);
+      });
+    for (auto& th : pool) th.join();
+  }
+  uint32_t v[8];
+  if (p.n) {
+    merkle_load(v, tr.row(p.top));
+    for (uint32_t g = p.top; g < p.depth; ++g) {
+      merkle_fold_step(v, p.first, g, (const uint32_t*)tr.ztab.data());
+      merkle_keep(tr.nodes.data(), p.lv[g + 1].base, p.lv[g + 1].count, p.lv[g + 1].off, p.lv[g + 1].base, v);
+    }
+  } else {
+    merkle_load(v, (const uint32_t*)tr.ztab.data() + 8 * p.depth);
+  }
+  if (mix) merkle_mix_in_length(v, length);
+  for (int w = 0; w < 8; ++w)
+    for (int b = 0; b < 4; ++b) root32[4 * w + b] = (uint8_t)(v[w] >> (24 - 8 * b));
+}
+
+// k_merkle_proofs: one (index, level) per iteration
+void hc_merkle_siblings(const HcTree& tr, size_t n_idx, const uint64_t* indices, uint64_t index_base, uint8_t* proofs,
+                        size_t stride) {
+  const MerklePlan& p = tr.p;
+  for (size_t k = 0; k < n_idx; ++k)
+    for (uint32_t h = 0; h < p.depth; ++h) {
+      const uint64_t i = indices ? indices[k] : index_base + k;
+      const bool kept = h == 0 || p.lv[h].off != MERKLE_NONE;
+      const uint32_t* row = kept ? tr.row(h) : tr.nodes.data();
+      const uint32_t* src = merkle_node_src(row, p.lv[h].base, kept ? p.lv[h].count : 0, (i >> h) ^ 1,
+                                            (const uint32_t*)tr.ztab.data() + 8 * h);
+      std::memcpy(proofs + k * stride + 32 * (size_t)h, src, 32);
+    }
+}
+}  // namespace
+
+// bls381_merkle_root: 0, or -2 for arguments the engine rejects
+int hc_merkle_root(size_t n, const uint8_t* leaves32, uint64_t first, uint32_t depth, int mix_length, uint64_t length,
+                   int threads, uint8_t* root32) {
+  if (!merkle_args_in_range(n, first, depth) || !root32 || (n && !leaves32)) return -2;
+  HcTree tr;
+  tr.p = plan_merkle(n, first, depth, false);
+  hc_merkle_tree(tr, leaves32, mix_length, length, threads, root32);
+  return 0;
+}
+
+// bls381_merkle_proofs: 0, or -2 for arguments the engine rejects
+int hc_merkle_proofs(size_t n, const uint8_t* leaves32, uint64_t first, uint32_t depth, size_t n_idx,
+                     const uint64_t* indices, uint8_t* proofs, size_t proof_stride, int threads, uint8_t* root32) {
+  if (!merkle_args_in_range(n, first, depth) || n_idx > (size_t)INT32_MAX || proof_stride < (size_t)32 * depth ||
+      !root32 || (n && !leaves32) || (n_idx && (!indices || (!proofs && depth))))
+    return -2;
+  HcTree tr;
+  tr.p = plan_merkle(n, first, depth, true);
+  hc_merkle_tree(tr, leaves32, 0, 0, threads, root32);
+  hc_merkle_siblings(tr, n_idx, indices, 0, proofs, proof_stride);
+  return 0;
+}
+
+// bls381_deposits_build: the leaves through DEPOSIT_ROOT_PROG, the kept tree, proofs and data
+int hc_deposits_build(size_t n, const uint8_t* deposit_data, uint64_t first_index, int threads, uint8_t* deposits,
+                      uint8_t* root32) {
+  if (!merkle_args_in_range(n, first_index, DEPOSIT_PROOF_DEPTH) || !root32 || (n && (!deposit_data || !deposits)))
+    return -2;
+  if (threads < 1) threads = 1;
+  std::vector<uint8_t> leaves(32 * n + 32);
+  std::vector<std::thread> pool;
+  for (int k = 0; k < threads; ++k)
+    pool.emplace_back([&, k] {
+      uint32_t stk[SSZ_STACK][8], r[8];
+      for (size_t i = (size_t)k; i < n; i += (size_t)threads) {
+        ssz_run(r, deposit_data + DEPOSIT_DATA_BYTES * i, DEPOSIT_ROOT_PROG, DEPOSIT_ROOT_PROG_LEN, stk);
+        for (int w = 0; w < 8; ++w)
+          for (int b = 0; b < 4; ++b) leaves[32 * i + 4 * w + b] = (uint8_t)(r[w] >> (24 - 8 * b));
+      }
+    });
+  for (auto& th : pool) th.join();
+  HcTree tr;
+  tr.p = plan_merkle(n, first_index, DEPOSIT_PROOF_DEPTH, true);
+  hc_merkle_tree(tr, leaves.data(), 0, 0, threads, root32);
+  hc_merkle_siblings(tr, n, nullptr, first_index, deposits, DEPOSIT_BYTES);
+  for (size_t i = 0; i < n; ++i)
+    std::memcpy(deposits + DEPOSIT_BYTES * i + DEPOSIT_PROOF_BYTES, deposit_data + DEPOSIT_DATA_BYTES * i,
+                DEPOSIT_DATA_BYTES);
+  return 0;
+}
+
+// plan_merkle and the workspace carves on the counting allocator.  levels: 65 x {base, count,
+// off}; passes: up to 16 x {h0, steps, tile0, tiles}; out: {pass count, top, node bytes, the
+// carve of the level table and the node slice, merkle_node_bound(n, depth)}.  0, or -2 for a
+// shape plan_merkle rejects.
+int hc_merkle_plan(uint64_t n, uint64_t first, uint32_t depth, int keep, uint64_t* levels, uint64_t* passes,
+                   uint64_t* out) {
+  if (!merkle_shape_ok(n, first, depth)) return -2;
+  const MerklePlan p = plan_merkle(n, first, depth, keep != 0);
+  for (uint32_t h = 0; h <= MERKLE_DEPTH_MAX; ++h) {
+    levels[3 * h] = p.lv[h].base;
+    levels[3 * h + 1] = p.lv[h].count;
+    levels[3 * h + 2] = p.lv[h].off;
+  }
+  if (p.passes.size() > 16) return -2;
+  for (size_t k = 0; k < p.passes.size(); ++k) {
+    passes[4 * k] = p.passes[k].h0;
+    passes[4 * k + 1] = p.passes[k].steps;
+    passes[4 * k + 2] = p.passes[k].tile0;
+    passes[4 * k + 3] = p.passes[k].tiles;
+  }
+  out[0] = p.passes.size();
+  out[1] = p.top;
+  out[2] = p.node_bytes;
+  out[3] = merkle_ws_size(n, first, depth, keep != 0);
+  out[4] = merkle_node_bound(n, depth);
+  return 0;
 }
 
 // get_shuffled_index (bls381_shuffle.hpp: the direct form, every position hashing its own source

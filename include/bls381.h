@@ -20,6 +20,12 @@
  *     `_device` variants take device pointers and a hipStream_t (as void*).
  *   - There is no CPU fallback: without a usable gfx950 device every call
  *     returns BLS381_ENODEV.
+ *
+ * Beside the BLS calls the header carries what produces and consumes their inputs
+ * on the device: the pubkey registry, SSZ roots of fixed-size containers,
+ * verify_merkle_branch and process_deposit, Merkle trees across items (roots and
+ * proofs of utils/merkle_minimal.py's trees, list roots with mix_in_length, the
+ * builder of Deposits with their proofs), and committee selection.
  */
 #ifndef BLS381_H
 #define BLS381_H
@@ -404,6 +410,67 @@ int bls381_registry_process_deposits_device(bls381_registry* reg, size_t n, cons
                                             const uint8_t dom8[8], int commit, uint8_t* d_outcome,
                                             int32_t* d_validator_index, int64_t* first_bad_proof, void* d_workspace,
                                             void* stream);
+
+/* ---- Merkle trees across items: list roots, deposit trees and proofs ----- */
+/* tree(leaves32[0..n), first, depth) is the tree with 2^depth leaves of which leaves
+ * first .. first+n-1 are given (32 bytes each) and every other one is the zero chunk; H is
+ * SHA-256, Z[0] = 32 zero bytes, Z[h+1] = H(Z[h] || Z[h]).  Node (h, j) covers leaves
+ * [j 2^h, (j+1) 2^h) and is Z[h] when that span misses the window.  This is the reference's
+ * utils/merkle_minimal.py: get_merkle_root / get_merkle_proof are first = 0, depth = 32 (a
+ * window with first > 0 is their tree over [ZERO] * first + leaves), merkleize_chunks is first = 0,
+ * depth = ceil(log2 n).  Extension: n == 0 is valid and gives Z[depth], the deposit contract's
+ * empty root, where the reference's get_merkle_root([]) raises.
+ *   root    node (depth, 0); with mix_length != 0 it is then mixed with `length`:
+ *           mix_in_length(root, length) = H(root || length as 32 bytes little-endian)
+ *           (ssz_impl.py:122-124).
+ *   proofs  for each of the n_idx leaf indices i, sibling h = node (h, (i >> h) ^ 1) for
+ *           h = 0 .. depth-1, 32 bytes each, at proofs + k * proof_stride (proof_stride >=
+ *           32 * depth; bytes of a row past the proof are left alone, so proofs can land in
+ *           the first 1,024 bytes of 1,208-byte Deposit records).  An index outside the window
+ *           gets the proof of a zero leaf; indices are meant to be below 2^depth.  With
+ *           depth == 0 nothing is written.  The root is not mixed.
+ * BLS381_EARG: depth > 64, first + n overflowing or above 2^depth, n or n_idx above 2^31 - 1,
+ * a proof_stride below 32 * depth, or a NULL argument that is needed (leaves with n > 0;
+ * indices and proofs with n_idx > 0; the root and, in the device forms, the workspace always).
+ * The device forms are queued on `stream`, not synchronised; d_leaves32, d_proofs and proof_stride
+ * are 4-byte aligned and d_indices 8-byte aligned (else BLS381_EARG); the workspace holds
+ * bls381_merkle_root_workspace_size / bls381_merkle_proofs_workspace_size bytes (0 for arguments
+ * the call rejects). */
+size_t bls381_merkle_root_workspace_size(size_t n, uint64_t first, uint32_t depth);
+int bls381_merkle_root(size_t n, const uint8_t* leaves32, uint64_t first, uint32_t depth, int mix_length,
+                       uint64_t length, uint8_t root[32]);
+int bls381_merkle_root_device(size_t n, const uint8_t* d_leaves32, uint64_t first, uint32_t depth, int mix_length,
+                              uint64_t length, uint8_t* d_root32, void* d_workspace, void* stream);
+size_t bls381_merkle_proofs_workspace_size(size_t n, uint64_t first, uint32_t depth);
+int bls381_merkle_proofs(size_t n, const uint8_t* leaves32, uint64_t first, uint32_t depth, size_t n_idx,
+                         const uint64_t* indices, uint8_t* proofs, size_t proof_stride, uint8_t root[32]);
+int bls381_merkle_proofs_device(size_t n, const uint8_t* d_leaves32, uint64_t first, uint32_t depth, size_t n_idx,
+                                const uint64_t* d_indices, uint8_t* d_proofs, size_t proof_stride, uint8_t* d_root32,
+                                void* d_workspace, void* stream);
+
+/* hash_tree_root of a List or Vector of n fixed-size composite elements (ssz_impl.py:143-155):
+ * the n items through a root program (as bls381_ssz_root_batch), then the tree of depth
+ * ceil(log2 n) over their roots, then mix_in_length(n) when mix_length != 0 (a List; a Vector
+ * has none).  n == 0 gives the zero chunk, mixed with 0 for a list.  BLS381_EARG as for
+ * bls381_ssz_root_batch, and for n above 2^31 - 1. */
+size_t bls381_ssz_list_root_workspace_size(size_t n);
+int bls381_ssz_list_root(size_t n, const uint8_t* items, size_t item_size, const uint32_t* prog, uint32_t prog_len,
+                         int mix_length, uint8_t root[32]);
+int bls381_ssz_list_root_device(size_t n, const uint8_t* d_items, size_t stride, size_t item_size,
+                                const uint32_t* h_prog, uint32_t prog_len, int mix_length, uint8_t* d_root32,
+                                void* d_workspace, void* stream);
+
+/* n serialized DepositData (184 B each) -> n serialized Deposits (1,208 B: the 32-sibling proof,
+ * then the data) under one deposit root: leaf first_index + i is hash_tree_root(data i), every
+ * other leaf of the depth-32 tree is zero (the reference's test/helpers/deposits.py build, the
+ * input of bls381_registry_process_deposits with the same first_index and root).
+ * BLS381_EARG: first_index + n above 2^32, n above 2^31 - 1, a NULL argument that is needed;
+ * d_deposits is 4-byte aligned. */
+size_t bls381_deposits_build_workspace_size(size_t n);
+int bls381_deposits_build(size_t n, const uint8_t* deposit_data, uint64_t first_index, uint8_t* deposits,
+                          uint8_t deposit_root[32]);
+int bls381_deposits_build_device(size_t n, const uint8_t* d_deposit_data, uint64_t first_index, uint8_t* d_deposits,
+                                 uint8_t* d_deposit_root32, void* d_workspace, void* stream);
 
 /* ---- committees: the producer of the grouped verify's d_entries ---------- */
 /* get_shuffled_index (0_beacon-chain.md:860-882) for positions first .. first+count-1 of a list of
