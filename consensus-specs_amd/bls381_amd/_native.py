@@ -122,6 +122,27 @@ _SIGS = {
     "bls381_deposits_build_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
     "bls381_deposits_build": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, _u8p, _u8p]),
     "bls381_deposits_build_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_deposit_tree_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
+    "bls381_deposit_tree_destroy": (None, [ctypes.c_void_p]),
+    "bls381_deposit_tree_count": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bls381_deposit_tree_capacity": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bls381_deposit_tree_append": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p]),
+    "bls381_deposit_tree_append_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p]),
+    "bls381_deposit_tree_append_data_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_deposit_tree_append_data": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p]),
+    "bls381_deposit_tree_append_data_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, _u8p]),
+    "bls381_deposit_tree_roots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p]),
+    "bls381_deposit_tree_roots_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, _u8p]),
+    "bls381_deposit_tree_proofs_workspace_size": (ctypes.c_size_t, [ctypes.c_uint32]),
+    "bls381_deposit_tree_proofs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_size_t, _u8p, _u8p,
+                                                  ctypes.c_size_t, _u8p]),
+    "bls381_deposit_tree_proofs_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_size_t, _u8p, _u8p,
+                                                         ctypes.c_size_t, _u8p, _u8p, _u8p]),
+    "bls381_deposit_tree_deposits_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_deposit_tree_deposits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t,
+                                                    _u8p, _u8p]),
+    "bls381_deposit_tree_deposits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                           ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p]),
     "bls381_shuffle_workspace_size": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]),
     "bls381_shuffle": (ctypes.c_int, [ctypes.c_uint64, _u8p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _u8p,
                                       _u8p]),

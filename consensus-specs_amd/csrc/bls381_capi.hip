@@ -2046,6 +2046,305 @@ int bls381_deposits_build(size_t n, const uint8_t* deposit_data, uint64_t first_
   });
 }
 
+// ---- the deposit tree kept on the device (storage and rules: bls381_deptree.hpp)
+// `count` is the host's: it moves when an append is queued, and every query checks against it.
+struct bls381_deposit_tree {
+  int device = -1;
+  deptree_shape sh{};
+  uint64_t count = 0;
+  uint8_t* store = nullptr;
+};
+
+int bls381_deposit_tree_create(size_t capacity, uint32_t depth, bls381_deposit_tree** out) {
+  if (!out) return BLS381_EARG;
+  *out = nullptr;
+  if (!deptree_args_ok(capacity, depth)) return BLS381_EARG;
+  int rc = 0;
+  Ctx* c = get_ctx(&rc);
+  if (!c) return rc;
+  std::unique_ptr<bls381_deposit_tree> t(new bls381_deposit_tree());
+  uint64_t bytes = 0;
+  t->device = c->device;
+  t->sh = deptree_make_shape(capacity, depth, &bytes);
+  if (hipMalloc(&t->store, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    t_err = "deposit tree allocation failed";
+    return BLS381_EHIP;
+  }
+  *out = t.release();
+  return 0;
+}
+
+void bls381_deposit_tree_destroy(bls381_deposit_tree* tree) {
+  if (!tree) return;
+  (void)hipSetDevice(tree->device);
+  (void)hipDeviceSynchronize();   // calls queued on the caller's streams may still read the store
+  (void)hipFree(tree->store);
+  delete tree;
+}
+
+size_t bls381_deposit_tree_count(const bls381_deposit_tree* tree) { return tree ? (size_t)tree->count : 0; }
+size_t bls381_deposit_tree_capacity(const bls381_deposit_tree* tree) { return tree ? (size_t)tree->sh.capacity : 0; }
+
+static Ctx* deptree_ctx(const bls381_deposit_tree* tree, int* rc) {
+  Ctx* c = get_ctx(rc);
+  if (c && c->device != tree->device) { t_err = "deposit tree belongs to another device"; *rc = BLS381_EARG; return nullptr; }
+  return c;
+}
+static bool deptree_fits(const bls381_deposit_tree* tree, size_t n) {
+  return n <= tree->sh.capacity - tree->count;
+}
+static uint8_t* deptree_leaf_row(bls381_deposit_tree* tree) { return tree->store + 32 * tree->count; }
+
+// Queues the passes of an append of n leaves that already sit in row 0 behind the count, then moves the count.
+static int deptree_append_impl(Ctx* c, bls381_deposit_tree* tree, size_t n, hipStream_t s) {
+  const deptree_levels lv{tree->sh, tree->count, tree->count + n};
+  for (const merkle_pass& ps : deptree_append_plan(tree->sh, tree->count, n))
+    LAUNCH("deptree_append", s, dim3((unsigned)ps.tiles), dim3(MERKLE_TILE / 2), k_deptree_append, tree->store, lv,
+           (const uint8_t*)c->ztab, ps.h0, ps.steps, ps.tile0);
+  tree->count += n;
+  return 0;
+}
+
+int bls381_deposit_tree_append_device(bls381_deposit_tree* tree, size_t n, const uint8_t* d_leaves32, void* stream) {
+  return guarded([&]() -> int {
+    if (!tree || !deptree_fits(tree, n) || (n && !d_leaves32) || !aligned4(d_leaves32)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(hipMemcpyAsync(deptree_leaf_row(tree), d_leaves32, 32 * n, hipMemcpyDeviceToDevice, s));
+    return deptree_append_impl(c, tree, n, s);
+  });
+}
+
+int bls381_deposit_tree_append(bls381_deposit_tree* tree, size_t n, const uint8_t* leaves32) {
+  return guarded([&]() -> int {
+    if (!tree || !deptree_fits(tree, n) || (n && !leaves32)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    TRY(hc.upload(deptree_leaf_row(tree), leaves32, 32 * n));
+    TRY(deptree_append_impl(c, tree, n, hc.s));
+    return hc.finish();
+  });
+}
+
+size_t bls381_deposit_tree_append_data_workspace_size(size_t n) {
+  return n > (size_t)INT32_MAX ? 0 : bls381_ssz_root_workspace_size();
+}
+
+// the leaves hash_tree_root(DepositData) written straight into row 0
+int bls381_deposit_tree_append_data_device(bls381_deposit_tree* tree, size_t n, const uint8_t* d_deposit_data,
+                                           void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!tree || n > (size_t)INT32_MAX || !deptree_fits(tree, n) || (n && (!d_deposit_data || !d_workspace)))
+      return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_ssz_root_workspace_size());
+    TRY(ssz_root_impl(n, d_deposit_data, DEPOSIT_DATA_BYTES, DEPOSIT_ROOT_PROG, DEPOSIT_ROOT_PROG_LEN,
+                      deptree_leaf_row(tree), carve_ssz(b), s, c));
+    return deptree_append_impl(c, tree, n, s);
+  });
+}
+
+int bls381_deposit_tree_append_data(bls381_deposit_tree* tree, size_t n, const uint8_t* deposit_data) {
+  return guarded([&]() -> int {
+    if (!tree || n > (size_t)INT32_MAX || !deptree_fits(tree, n) || (n && !deposit_data)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t *d_data, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_data = b.take<uint8_t>(DEPOSIT_DATA_BYTES * n);
+      d_ws = b.take<uint8_t>(bls381_deposit_tree_append_data_workspace_size(n));
+    }));
+    TRY(hc.upload(d_data, deposit_data, DEPOSIT_DATA_BYTES * n));
+    TRY(bls381_deposit_tree_append_data_device(tree, n, d_data, d_ws, hc.s));
+    return hc.finish();
+  });
+}
+
+static bool deptree_counts_ok(const bls381_deposit_tree* tree, size_t m, const uint64_t* counts) {
+  for (size_t q = 0; q < m; ++q)
+    if (counts[q] > tree->count) return false;
+  return true;
+}
+
+int bls381_deposit_tree_roots_device(bls381_deposit_tree* tree, size_t m, const uint64_t* h_counts, uint8_t* d_roots32,
+                                     void* stream) {
+  return guarded([&]() -> int {
+    if (!tree || m > (size_t)INT32_MAX || (m && (!h_counts || !d_roots32)) || !aligned4(d_roots32) ||
+        !deptree_counts_ok(tree, m, h_counts))
+      return BLS381_EARG;
+    if (m == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    // the counts travel as kernel arguments, DEPTREE_ROOTS_CHUNK a launch: nothing to keep alive
+    for (size_t q0 = 0; q0 < m; q0 += DEPTREE_ROOTS_CHUNK) {
+      const uint32_t mm = (uint32_t)std::min<size_t>(DEPTREE_ROOTS_CHUNK, m - q0);
+      deptree_counts ck{};
+      for (uint32_t q = 0; q < mm; ++q) ck.k[q] = (uint32_t)h_counts[q0 + q];
+      LAUNCH("deptree_roots", (hipStream_t)stream, dim3(grid_for(mm, 64)), dim3(64), k_deptree_roots, mm, ck,
+             (const uint8_t*)tree->store, tree->sh, (const uint8_t*)c->ztab, d_roots32 + 32 * q0);
+    }
+    return 0;
+  });
+}
+
+int bls381_deposit_tree_roots(bls381_deposit_tree* tree, size_t m, const uint64_t* counts, uint8_t* roots32) {
+  return guarded([&]() -> int {
+    if (!tree || m > (size_t)INT32_MAX || (m && (!counts || !roots32)) || !deptree_counts_ok(tree, m, counts))
+      return BLS381_EARG;
+    if (m == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t* d_roots;
+    TRY(hc.carve([&](Bump& b) { d_roots = b.take<uint8_t>(32 * m); }));
+    TRY(bls381_deposit_tree_roots_device(tree, m, counts, d_roots, hc.s));
+    TRY(hc.download(roots32, d_roots, 32 * m));
+    return hc.finish();
+  });
+}
+
+// the workspace of a proofs query: P[0 .. depth]
+size_t bls381_deposit_tree_proofs_workspace_size(uint32_t depth) {
+  if (depth == 0 || depth > DEPTREE_DEPTH_MAX) return 0;
+  return carved_bytes([&](Bump& b) { b.take<uint8_t>(32 * (size_t)(depth + 1)); });
+}
+
+// the P chain of count k into the workspace and d_root, then the siblings
+static int deptree_proofs_impl(Ctx* c, const bls381_deposit_tree* tree, uint64_t k, size_t n_idx,
+                               const uint64_t* d_indices, uint64_t index_base, uint8_t* d_proofs, size_t stride,
+                               uint8_t* d_root, void* ws, hipStream_t s) {
+  Bump b(ws, bls381_deposit_tree_proofs_workspace_size(tree->sh.depth));
+  uint8_t* ptab = b.take<uint8_t>(32 * (size_t)(tree->sh.depth + 1));
+  LAUNCH("deptree_chain", s, dim3(1), dim3(64), k_deptree_chain, k, (const uint8_t*)tree->store, tree->sh,
+         (const uint8_t*)c->ztab, ptab, d_root);
+  LAUNCH("deptree_gather", s, dim3(grid_for(n_idx * tree->sh.depth)), dim3(KBLOCK), k_deptree_gather, n_idx, d_indices,
+         index_base, k, (const uint8_t*)tree->store, tree->sh, (const uint8_t*)ptab, (const uint8_t*)c->ztab, d_proofs,
+         stride);
+  return 0;
+}
+static bool deptree_proofs_args_ok(const bls381_deposit_tree* tree, uint64_t k, size_t n_idx, const void* indices,
+                                   const void* proofs, size_t proof_stride, const void* root) {
+  if (!tree || k > tree->count || n_idx > (size_t)INT32_MAX || proof_stride < (size_t)32 * tree->sh.depth) return false;
+  return root && (n_idx == 0 || (indices && proofs));
+}
+
+int bls381_deposit_tree_proofs_device(bls381_deposit_tree* tree, uint64_t k, size_t n_idx, const uint64_t* d_indices,
+                                      uint8_t* d_proofs, size_t proof_stride, uint8_t* d_root32, void* d_workspace,
+                                      void* stream) {
+  return guarded([&]() -> int {
+    if (!deptree_proofs_args_ok(tree, k, n_idx, d_indices, d_proofs, proof_stride, d_root32) || !d_workspace ||
+        !aligned4(d_proofs) || (proof_stride & 3) || ((uintptr_t)d_indices & 7))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    return deptree_proofs_impl(c, tree, k, n_idx, d_indices, 0, d_proofs, proof_stride, d_root32, d_workspace,
+                               (hipStream_t)stream);
+  });
+}
+
+int bls381_deposit_tree_proofs(bls381_deposit_tree* tree, uint64_t k, size_t n_idx, const uint64_t* indices,
+                               uint8_t* proofs, size_t proof_stride, uint8_t root[32]) {
+  return guarded([&]() -> int {
+    if (!deptree_proofs_args_ok(tree, k, n_idx, indices, proofs, proof_stride, root)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_deposit_tree_proofs_workspace_size(tree->sh.depth), row = (size_t)32 * tree->sh.depth;
+    uint8_t *d_proofs, *d_root, *d_ws;
+    uint64_t* d_idx;
+    TRY(hc.carve([&](Bump& b) {
+      d_idx = b.take<uint64_t>(n_idx);
+      d_proofs = b.take<uint8_t>(row * n_idx);
+      d_root = b.take<uint8_t>(32);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_idx, indices, 8 * n_idx));
+    TRY(bls381_deposit_tree_proofs_device(tree, k, n_idx, d_idx, d_proofs, row, d_root, d_ws, hc.s));
+    // packed on the device; the caller's rows are proof_stride apart and only their proofs are written
+    if (n_idx) HIPC(hipMemcpy2DAsync(proofs, proof_stride, d_proofs, row, row, n_idx, hipMemcpyDeviceToHost, hc.s));
+    TRY(hc.download(root, d_root, 32));
+    return hc.finish();
+  });
+}
+
+// Deposits for leaves first_index .. first_index + n - 1 under the root at count k: each proof
+// into its record, the data copied behind it.  The workspace: the root (unused by the caller),
+// then the proofs query's own.
+size_t bls381_deposit_tree_deposits_workspace_size(size_t n) {
+  if (n > (size_t)INT32_MAX) return 0;
+  return carved_bytes([&](Bump& b) {
+    b.take<uint8_t>(32);
+    b.take<uint8_t>(bls381_deposit_tree_proofs_workspace_size(DEPOSIT_PROOF_DEPTH));
+  });
+}
+static bool deptree_deposits_args_ok(const bls381_deposit_tree* tree, uint64_t k, uint64_t first_index, size_t n,
+                                     const void* data, const void* deposits) {
+  if (!tree || tree->sh.depth != DEPOSIT_PROOF_DEPTH || n > (size_t)INT32_MAX || k > tree->count) return false;
+  return first_index <= k && n <= k - first_index && (n == 0 || (data && deposits));
+}
+
+int bls381_deposit_tree_deposits_device(bls381_deposit_tree* tree, uint64_t k, uint64_t first_index, size_t n,
+                                        const uint8_t* d_deposit_data, uint8_t* d_deposits, void* d_workspace,
+                                        void* stream) {
+  return guarded([&]() -> int {
+    if (!deptree_deposits_args_ok(tree, k, first_index, n, d_deposit_data, d_deposits) || !d_workspace ||
+        !aligned4(d_deposits))
+      return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_deposit_tree_deposits_workspace_size(n));
+    uint8_t* d_root = b.take<uint8_t>(32);
+    void* ws = b.take<uint8_t>(bls381_deposit_tree_proofs_workspace_size(DEPOSIT_PROOF_DEPTH));
+    TRY(deptree_proofs_impl(c, tree, k, n, nullptr, first_index, d_deposits, DEPOSIT_BYTES, d_root, ws, s));
+    LAUNCH("deposit_data_copy", s, dim3(grid_for(DEPOSIT_DATA_BYTES * n)), dim3(KBLOCK), k_scatter_field, n,
+           d_deposit_data, (uint32_t)DEPOSIT_DATA_BYTES, d_deposits, DEPOSIT_BYTES, (uint32_t)DEPOSIT_PROOF_BYTES);
+    return 0;
+  });
+}
+
+int bls381_deposit_tree_deposits(bls381_deposit_tree* tree, uint64_t k, uint64_t first_index, size_t n,
+                                 const uint8_t* deposit_data, uint8_t* deposits) {
+  return guarded([&]() -> int {
+    if (!deptree_deposits_args_ok(tree, k, first_index, n, deposit_data, deposits)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = deptree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t *d_data, *d_dep, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_data = b.take<uint8_t>(DEPOSIT_DATA_BYTES * n);
+      d_dep = b.take<uint8_t>(DEPOSIT_BYTES * n);
+      d_ws = b.take<uint8_t>(bls381_deposit_tree_deposits_workspace_size(n));
+    }));
+    TRY(hc.upload(d_data, deposit_data, DEPOSIT_DATA_BYTES * n));
+    TRY(bls381_deposit_tree_deposits_device(tree, k, first_index, n, d_data, d_dep, d_ws, hc.s));
+    TRY(hc.download(deposits, d_dep, DEPOSIT_BYTES * n));
+    return hc.finish();
+  });
+}
+
 static_assert(BLS381_DEPOSIT_SKIPPED == DEP_SKIPPED && BLS381_DEPOSIT_NEW == DEP_NEW &&
                   BLS381_DEPOSIT_TOPUP == DEP_TOPUP && BLS381_DEPOSIT_BYTES == DEPOSIT_BYTES,
               "include/bls381.h and the kernels agree on the deposit constants");

@@ -13,6 +13,7 @@
 #include "bls381_quad.hpp"
 #include "bls381_ssz.hpp"
 #include "bls381_merkle.hpp"
+#include "bls381_deptree.hpp"
 #include "bls381_shuffle.hpp"
 
 namespace bls381 {
@@ -1547,26 +1548,37 @@ typedef __attribute__((address_space(1))) const merkle_level g_clevel;
 // nodes, aligned to MERKLE_TILE in absolute node index -- `steps` levels up.  Each lane hashes
 // one pair read from `in` (the row of level h0: its real nodes, 32 bytes each; a node outside
 // them is Z[h0] from ztab), then the tile is halved in LDS.  Node j of level h0 + s is written
-// to its row of `nodes` when the level table says the level is kept and the node real; a
+// to its row of `nodes` when the levels say the level is kept and the node real; a
 // virtual node's value is Z of its level, by hashing, and is written nowhere.
-__global__ void __launch_bounds__(MERKLE_TILE / 2) k_merkle_reduce(const uint8_t* __restrict__ in, uint8_t* nodes,
-                                                                  const merkle_level* __restrict__ lv,
-                                                                  const uint8_t* __restrict__ ztab, uint32_t h0,
-                                                                  uint32_t steps, uint64_t tile0) {
+// lv.in(h) is the level a tile reads, lv.out(h) the one it writes: the same table entry for a
+// windowed tree (merkle_table_levels), the stored row and its not yet complete nodes for an
+// append to a deposit tree (deptree_levels: bls381_deptree.hpp).
+struct merkle_table_levels {
+  g_clevel* L;
+  __device__ __forceinline__ merkle_level in(uint32_t h) const { return {L[h].base, L[h].count, L[h].off}; }
+  __device__ __forceinline__ merkle_level out(uint32_t h) const { return in(h); }
+};
+template <class Lv>
+__device__ __forceinline__ void merkle_reduce_tile(const uint8_t* __restrict__ in, uint8_t* nodes, const Lv& lv,
+                                                   const uint8_t* __restrict__ ztab, uint32_t h0, uint32_t steps,
+                                                   uint64_t tile0) {
   constexpr uint32_t T = MERKLE_TILE / 2;
   __shared__ uint32_t tile[2][8][MERKLE_LDS_ROW];
   const uint32_t l = threadIdx.x;
   const uint64_t t = tile0 + blockIdx.x;
-  g_clevel* L = (g_clevel*)lv;
   g_u32* out = (g_u32*)nodes;
   uint64_t j = t * T + l;
   uint32_t v[8];
-  merkle_first_step(v, (g_cu32*)in, L[h0].base, L[h0].count, j, (g_cu32*)(ztab + 32 * h0));
+  const merkle_level src = lv.in(h0);
+  merkle_first_step(v, (g_cu32*)in, src.base, src.count, j, (g_cu32*)(ztab + 32 * h0));
   bool live = true;
   uint32_t p = 0;
   for (uint32_t s = 1;; ++s) {
     // v: node j of level h0 + s, in the lanes that are live
-    if (live) merkle_keep(out, L[h0 + s].base, L[h0 + s].count, L[h0 + s].off, j, v);
+    if (live) {
+      const merkle_level o = lv.out(h0 + s);
+      merkle_keep(out, o.base, o.count, o.off, j, v);
+    }
     if (s == steps) break;
     if (live)
       for (int w = 0; w < 8; ++w) tile[p][w][merkle_lds_slot(l)] = v[w];
@@ -1583,6 +1595,12 @@ __global__ void __launch_bounds__(MERKLE_TILE / 2) k_merkle_reduce(const uint8_t
     j = ((t * T) >> s) + l;
     p ^= 1;
   }
+}
+__global__ void __launch_bounds__(MERKLE_TILE / 2) k_merkle_reduce(const uint8_t* __restrict__ in, uint8_t* nodes,
+                                                                  const merkle_level* __restrict__ lv,
+                                                                  const uint8_t* __restrict__ ztab, uint32_t h0,
+                                                                  uint32_t steps, uint64_t tile0) {
+  merkle_reduce_tile(in, nodes, merkle_table_levels{(g_clevel*)lv}, ztab, h0, steps, tile0);
 }
 
 // The last step, one lane: the single real node of level `top` (node: its 32 bytes, or null for
@@ -1642,6 +1660,70 @@ __global__ void __launch_bounds__(KBLOCK) k_scatter_field(size_t n, const uint8_
   if (t >= n * len) return;
   const size_t i = t / len, b = t % len;
   items[i * stride + off + b] = in[t];
+}
+
+// ------------------------------------------------- the deposit tree kept in memory --
+// (storage, the append's levels and the query rule: bls381_deptree.hpp)
+// One pass of an append that takes the count from lv.c0 to lv.c1: the tile reduction above over
+// the stored row of level h0, writing the nodes that were not complete at c0.  Everything the
+// pass knows about the tree travels in `lv`, by value.
+__global__ void __launch_bounds__(MERKLE_TILE / 2) k_deptree_append(uint8_t* store, deptree_levels lv,
+                                                                   const uint8_t* __restrict__ ztab, uint32_t h0,
+                                                                   uint32_t steps, uint64_t tile0) {
+  merkle_reduce_tile(store + lv.sh.off[h0], store, lv, ztab, h0, steps, tile0);
+}
+
+// counts of one k_deptree_roots launch: they are host values and travel as kernel arguments
+constexpr uint32_t DEPTREE_ROOTS_CHUNK = 512;
+struct deptree_counts {
+  uint32_t k[DEPTREE_ROOTS_CHUNK];   // a count is at most the capacity, below 2^32
+};
+// Root(k) for m counts, one lane each: the P chain, depth dependent hashes.
+__global__ void __launch_bounds__(64) k_deptree_roots(uint32_t m, deptree_counts counts,
+                                                      const uint8_t* __restrict__ store, deptree_shape sh,
+                                                      const uint8_t* __restrict__ ztab, uint8_t* __restrict__ roots) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= m) return;
+  const uint64_t k = counts.k[q];
+  uint32_t v[8];
+  merkle_load(v, (g_cu32*)ztab);
+  for (uint32_t h = 0; h < sh.depth; ++h) deptree_chain_step(v, sh, (g_cu32*)store, k, h, (g_cu32*)ztab);
+  merkle_store((g_u32*)(roots + 32 * (size_t)q), v);
+}
+
+// The P chain of one count, one lane: P[0 .. depth] to ptab (32 bytes each), P[depth] to root.
+__global__ void __launch_bounds__(64) k_deptree_chain(uint64_t k, const uint8_t* __restrict__ store, deptree_shape sh,
+                                                      const uint8_t* __restrict__ ztab, uint8_t* __restrict__ ptab,
+                                                      uint8_t* __restrict__ root) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t v[8];
+  merkle_load(v, (g_cu32*)ztab);
+  for (uint32_t h = 0;; ++h) {
+    merkle_store((g_u32*)(ptab + 32 * h), v);
+    if (h == sh.depth) break;
+    deptree_chain_step(v, sh, (g_cu32*)store, k, h, (g_cu32*)ztab);
+  }
+  for (int w = 0; w < 8; ++w)
+    for (int b = 0; b < 4; ++b) root[4 * w + b] = (uint8_t)(v[w] >> (24 - 8 * b));
+}
+
+// The proofs at count k of n_idx leaf indices (indices[t], or index_base + t when indices is
+// null), one lane per sibling: a stored complete node, P[h] or Z[h], to proofs + t proof_stride
+// + 32 h (4-byte aligned), as k_merkle_proofs.
+__global__ void __launch_bounds__(KBLOCK) k_deptree_gather(size_t n_idx, const uint64_t* __restrict__ indices,
+                                                           uint64_t index_base, uint64_t k,
+                                                           const uint8_t* __restrict__ store, deptree_shape sh,
+                                                           const uint8_t* __restrict__ ptab,
+                                                           const uint8_t* __restrict__ ztab,
+                                                           uint8_t* __restrict__ proofs, size_t proof_stride) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_idx * sh.depth) return;
+  const size_t q = t / sh.depth;
+  const uint32_t h = (uint32_t)(t % sh.depth);
+  const uint64_t i = indices ? indices[q] : index_base + q;
+  g_cu32* src = deptree_sibling_src(sh, (g_cu32*)store, k, i, h, (g_cu32*)ptab, (g_cu32*)ztab);
+  g_u32* dst = (g_u32*)(proofs + q * proof_stride + 32 * h);
+  for (int w = 0; w < 8; ++w) dst[w] = src[w];
 }
 
 // outcomes of process_deposit (include/bls381.h BLS381_DEPOSIT_*)

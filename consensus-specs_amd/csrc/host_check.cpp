@@ -23,6 +23,7 @@
 #include "bls381_shuffle.hpp"
 #include "bls381_ssz.hpp"
 #include "bls381_merkle.hpp"
+#include "bls381_deptree.hpp"
 
 // ---- stand-ins for the HIP types and runtime calls that bls381_scope.hpp is written against.
 // Every call appends one line to a log (hc_scope_scenario, at the end of this file, returns it);
@@ -545,22 +546,30 @@ struct HcTree {
   const uint32_t* row(uint32_t h) const { return h == 0 ? leaves.data() : nodes.data() + p.lv[h].off / 4; }
 };
 
-// one workgroup of k_merkle_reduce: tile t of pass ps
-void hc_merkle_tile_run(HcTree& tr, const merkle_pass& ps, uint64_t t) {
+// one workgroup of the tile reduction (bls381_kernels.hpp merkle_reduce_tile): tile t of pass ps
+// over the row `in`, writing into `nodes`; lv.in(h) is the level read, lv.out(h) the one written
+extern "C++" {
+struct HcTableLevels {
+  const merkle_level* L;
+  merkle_level in(uint32_t h) const { return L[h]; }
+  merkle_level out(uint32_t h) const { return L[h]; }
+};
+template <class Lv>
+void hc_merkle_tile_run(const uint32_t* in, uint32_t* nodes, const Lv& lv, const uint32_t* ztab, const merkle_pass& ps,
+                        uint64_t t) {
   constexpr uint32_t T = MERKLE_TILE / 2;
   static thread_local uint32_t tile[2][8][MERKLE_LDS_ROW];
-  const merkle_level* L = tr.p.lv;
   uint32_t v[T][8];
+  const merkle_level src = lv.in(ps.h0);
   for (uint32_t l = 0; l < T; ++l) {
     const uint64_t j = t * T + l;
-    merkle_first_step(v[l], tr.row(ps.h0), L[ps.h0].base, L[ps.h0].count, j,
-                      (const uint32_t*)tr.ztab.data() + 8 * ps.h0);
+    merkle_first_step(v[l], in, src.base, src.count, j, ztab + 8 * ps.h0);
   }
   uint32_t p = 0, live = T;
   for (uint32_t s = 1;; ++s) {
-    const merkle_level& o = L[ps.h0 + s];
+    const merkle_level o = lv.out(ps.h0 + s);
     for (uint32_t l = 0; l < live; ++l)
-      merkle_keep(tr.nodes.data(), o.base, o.count, o.off, ((t * T) >> (s - 1)) + l, v[l]);
+      merkle_keep(nodes, o.base, o.count, o.off, ((t * T) >> (s - 1)) + l, v[l]);
     if (s == ps.steps) break;
     for (uint32_t l = 0; l < live; ++l)
       for (int w = 0; w < 8; ++w) tile[p][w][merkle_lds_slot(l)] = v[l][w];
@@ -576,6 +585,19 @@ void hc_merkle_tile_run(HcTree& tr, const merkle_pass& ps, uint64_t t) {
     p ^= 1;
   }
 }
+// the tiles of a pass dealt to `threads` host threads
+template <class Lv>
+void hc_merkle_pass_run(const uint32_t* in, uint32_t* nodes, const Lv& lv, const uint32_t* ztab, const merkle_pass& ps,
+                        int threads) {
+  std::vector<std::thread> pool;
+  for (int k = 0; k < threads; ++k)
+    pool.emplace_back([&, k] {
+      for (uint64_t b = (uint64_t)k; b < ps.tiles; b += (uint64_t)threads)
+        hc_merkle_tile_run(in, nodes, lv, ztab, ps, ps.tile0 + b);
+    });
+  for (auto& th : pool) th.join();
+}
+}  // extern "C++"
 
 // the whole tree: the passes, then k_merkle_finish's fold, mix and root
 void hc_merkle_tree(HcTree& tr, const uint8_t* leaves32, int mix, uint64_t length, int threads, uint8_t* root32) {
@@ -589,14 +611,8 @@ void hc_merkle_tree(HcTree& tr, const uint8_t* leaves32, int mix, uint64_t lengt
   tr.ztab.assign(MERKLE_ZERO_TABLE_BYTES / 4, 0);
   std::memcpy(tr.ztab.data(), z, sizeof(z));
   if (threads < 1) threads = 1;
-  for (const merkle_pass& ps : p.passes) {
-    std::vector<std::thread> pool;
-    for (int k = 0; k < threads; ++k)
-      pool.emplace_back([&tr, &ps, k, threads] {
-        for (uint64_t b = (uint64_t)k; b < ps.tiles; b += (uint64_t)threads) hc_merkle_tile_run(tr, ps, ps.tile0 + b);
-      });
-    for (auto& th : pool) th.join();
-  }
+  for (const merkle_pass& ps : p.passes)
+    hc_merkle_pass_run(tr.row(ps.h0), tr.nodes.data(), HcTableLevels{p.lv}, tr.ztab.data(), ps, threads);
   uint32_t v[8];
   if (p.n) {
     merkle_load(v, tr.row(p.top));
@@ -704,6 +720,107 @@ int hc_merkle_plan(uint64_t n, uint64_t first, uint32_t depth, int keep, uint64_
   out[2] = p.node_bytes;
   out[3] = merkle_ws_size(n, first, depth, keep != 0);
   out[4] = merkle_node_bound(n, depth);
+  return 0;
+}
+
+// ---- the deposit tree kept in memory (bls381_deptree.hpp): what k_deptree_append / _roots /
+// _chain / _gather run, workgroups and lanes as plain loops.  The store has its exact size, so
+// the sanitized build sees any access outside it.
+namespace {
+struct HcDepTree {
+  deptree_shape sh{};
+  uint64_t count = 0;
+  std::vector<uint32_t> store, ztab;
+};
+}  // namespace
+
+void* hc_deptree_create(uint64_t capacity, uint32_t depth) {
+  if (!deptree_args_ok(capacity, depth)) return nullptr;
+  auto* t = new HcDepTree();
+  uint64_t bytes = 0;
+  t->sh = deptree_make_shape(capacity, depth, &bytes);
+  t->store.assign(bytes / 4, 0xEEEEEEEEu);
+  uint8_t z[MERKLE_ZERO_TABLE_BYTES];
+  merkle_zero_table(z);
+  t->ztab.assign(MERKLE_ZERO_TABLE_BYTES / 4, 0);
+  std::memcpy(t->ztab.data(), z, sizeof(z));
+  return t;
+}
+void hc_deptree_destroy(void* tree) { delete (HcDepTree*)tree; }
+uint64_t hc_deptree_count(const void* tree) { return tree ? ((const HcDepTree*)tree)->count : 0; }
+
+// bls381_deposit_tree_append: 0, or -2 for arguments the engine rejects
+int hc_deptree_append(void* tree, size_t n, const uint8_t* leaves32, int threads) {
+  HcDepTree* t = (HcDepTree*)tree;
+  if (!t || n > t->sh.capacity - t->count || (n && !leaves32)) return -2;
+  if (n == 0) return 0;
+  if (threads < 1) threads = 1;
+  std::memcpy(t->store.data() + 8 * t->count, leaves32, 32 * n);
+  const deptree_levels lv{t->sh, t->count, t->count + n};
+  for (const merkle_pass& ps : deptree_append_plan(t->sh, t->count, n))
+    hc_merkle_pass_run(t->store.data() + t->sh.off[ps.h0] / 4, t->store.data(), lv, t->ztab.data(), ps, threads);
+  t->count += n;
+  return 0;
+}
+
+// bls381_deposit_tree_roots (k_deptree_roots, one count per iteration): 0 or -2
+int hc_deptree_roots(void* tree, size_t m, const uint64_t* counts, uint8_t* roots32) {
+  HcDepTree* t = (HcDepTree*)tree;
+  if (!t || (m && (!counts || !roots32))) return -2;
+  for (size_t q = 0; q < m; ++q)
+    if (counts[q] > t->count) return -2;
+  for (size_t q = 0; q < m; ++q) {
+    uint32_t v[8];
+    merkle_load(v, (const uint32_t*)t->ztab.data());
+    for (uint32_t h = 0; h < t->sh.depth; ++h)
+      deptree_chain_step(v, t->sh, (const uint32_t*)t->store.data(), counts[q], h, (const uint32_t*)t->ztab.data());
+    uint32_t out[8];
+    merkle_store(out, v);
+    std::memcpy(roots32 + 32 * q, out, 32);
+  }
+  return 0;
+}
+
+// bls381_deposit_tree_proofs (k_deptree_chain, then k_deptree_gather): 0 or -2
+int hc_deptree_proofs(void* tree, uint64_t k, size_t n_idx, const uint64_t* indices, uint8_t* proofs,
+                      size_t proof_stride, uint8_t* root32) {
+  HcDepTree* t = (HcDepTree*)tree;
+  if (!t || k > t->count || n_idx > (size_t)INT32_MAX || proof_stride < (size_t)32 * t->sh.depth || !root32 ||
+      (n_idx && (!indices || !proofs)))
+    return -2;
+  const uint32_t* store = t->store.data();
+  const uint32_t* ztab = t->ztab.data();
+  std::vector<uint32_t> ptab(8 * (size_t)(t->sh.depth + 1));
+  uint32_t v[8];
+  merkle_load(v, ztab);
+  for (uint32_t h = 0;; ++h) {
+    merkle_store(ptab.data() + 8 * h, v);
+    if (h == t->sh.depth) break;
+    deptree_chain_step(v, t->sh, store, k, h, ztab);
+  }
+  std::memcpy(root32, ptab.data() + 8 * t->sh.depth, 32);
+  for (size_t q = 0; q < n_idx; ++q)
+    for (uint32_t h = 0; h < t->sh.depth; ++h)
+      std::memcpy(proofs + q * proof_stride + 32 * (size_t)h,
+                  deptree_sibling_src(t->sh, store, k, indices[q], h, (const uint32_t*)ptab.data(), ztab), 32);
+  return 0;
+}
+
+// deptree_append_plan for a tree of `capacity` (depth 32) at `count`: out = {pass count, then
+// {h0, steps, tile0, tiles} per pass, up to 8 passes}.  0, or -2 for a rejected shape or append.
+int hc_deptree_plan(uint64_t capacity, uint64_t count, uint64_t n, uint64_t* out) {
+  if (!deptree_args_ok(capacity, DEPTREE_DEPTH_MAX) || count > capacity || n > capacity - count) return -2;
+  uint64_t bytes = 0;
+  const deptree_shape sh = deptree_make_shape(capacity, DEPTREE_DEPTH_MAX, &bytes);
+  const std::vector<merkle_pass> passes = deptree_append_plan(sh, count, n);
+  if (passes.size() > 8) return -2;
+  out[0] = passes.size();
+  for (size_t k = 0; k < passes.size(); ++k) {
+    out[1 + 4 * k] = passes[k].h0;
+    out[2 + 4 * k] = passes[k].steps;
+    out[3 + 4 * k] = passes[k].tile0;
+    out[4 + 4 * k] = passes[k].tiles;
+  }
   return 0;
 }
 

@@ -472,6 +472,73 @@ int bls381_deposits_build(size_t n, const uint8_t* deposit_data, uint64_t first_
 int bls381_deposits_build_device(size_t n, const uint8_t* d_deposit_data, uint64_t first_index, uint8_t* d_deposits,
                                  uint8_t* d_deposit_root32, void* d_workspace, void* stream);
 
+/* ---- the deposit tree kept on the device: append, roots and proofs at any count ---- */
+/* A tree of 2^depth leaves (depth <= 32, the deposit contract's 32) that lives in device memory,
+ * grows by appends and answers for every count k up to the current one what the contract
+ * answers at that count: root(k) = get_deposit_root() after k deposits = the reference's
+ * get_merkle_root(leaves[:k]), and proofs under it (get_merkle_proof).  A block's deposits carry
+ * proofs against state.latest_eth1_data.deposit_root (0_beacon-chain.md:1630, :1742), the root
+ * at the voted count: not the tree of the block's batch, which is what bls381_deposits_build
+ * makes, and not the newest root.  Queries for a count are not disturbed by later appends: they
+ * read only nodes that were complete at that count.
+ * The tree belongs to the device current at creation (calls with another device current return
+ * BLS381_EARG) and holds about 64 bytes per leaf of capacity.  One thread and one stream at a
+ * time use a tree, or the caller orders them: the host-pointer forms run on the engine's own
+ * stream and return synchronised, the device forms are queued on `stream`, not synchronised.
+ * The count is kept on the host and moves when an append is queued.
+ *   create   the capacity is fixed.  BLS381_EARG for depth > 32, capacity == 0 or capacity >
+ *            2^depth - 1 (the contract's MAX_DEPOSIT_COUNT assert; depth 0 has no valid capacity).
+ *   append   leaves count .. count+n-1 become the n given 32-byte values; append_data takes n
+ *            serialized DepositData (184 B each) and appends leaf = hash_tree_root(data), hashed
+ *            straight into the tree.  n == 0 is BLS381_OK and runs nothing; count + n > capacity
+ *            is BLS381_EARG and leaves the tree unchanged.
+ *   roots    roots32[q] = the root of the depth-`depth` tree over the first counts[q] leaves with
+ *            zeros behind them; counts[q] == 0 gives Z[depth].  counts is host memory in both
+ *            forms.  Any counts[q] above the count is BLS381_EARG.
+ *   proofs   siblings 0 .. depth-1 of each index in the tree at count k, and that tree's root,
+ *            with the proof rows of bls381_merkle_proofs: proof_stride >= 32 * depth, bytes of a
+ *            row past the proof left alone; d_proofs and proof_stride 4-byte, d_indices 8-byte
+ *            aligned in the device form.  An index >= k gets the proof of a zero leaf.  k above
+ *            the count is BLS381_EARG.
+ *   deposits n serialized Deposits (1,208 B) for leaves first_index .. first_index+n-1: the proof
+ *            under the root at count k, then deposit_data[i] (184 B each) copied behind it; the
+ *            input of bls381_registry_process_deposits with the same first_index and
+ *            roots([k]).  Needs depth == 32 and first_index + n <= k <= count, else BLS381_EARG.
+ *            The data is NOT re-hashed against the stored leaves: handing in other data than was
+ *            appended gives deposits whose proofs fail.
+ * m, n and n_idx are at most 2^31 - 1; a NULL argument that is needed is BLS381_EARG (the tree
+ * always; data and outputs when the count of items is not 0; the root of `proofs` and the
+ * workspaces of the device forms always).  In the device forms d_leaves32, d_roots32 and
+ * d_deposits are 4-byte aligned as well, else BLS381_EARG.  Workspaces hold bls381_deposit_tree_*_workspace_size
+ * bytes (0 for arguments the call rejects) and belong to the call: a tree has no scratch of its
+ * own that a second queued call could overwrite. */
+typedef struct bls381_deposit_tree bls381_deposit_tree;
+int bls381_deposit_tree_create(size_t capacity, uint32_t depth, bls381_deposit_tree** out);
+void bls381_deposit_tree_destroy(bls381_deposit_tree* tree);
+size_t bls381_deposit_tree_count(const bls381_deposit_tree* tree);
+size_t bls381_deposit_tree_capacity(const bls381_deposit_tree* tree);
+int bls381_deposit_tree_append(bls381_deposit_tree* tree, size_t n, const uint8_t* leaves32);
+int bls381_deposit_tree_append_device(bls381_deposit_tree* tree, size_t n, const uint8_t* d_leaves32, void* stream);
+size_t bls381_deposit_tree_append_data_workspace_size(size_t n);
+int bls381_deposit_tree_append_data(bls381_deposit_tree* tree, size_t n, const uint8_t* deposit_data);
+int bls381_deposit_tree_append_data_device(bls381_deposit_tree* tree, size_t n, const uint8_t* d_deposit_data,
+                                           void* d_workspace, void* stream);
+int bls381_deposit_tree_roots(bls381_deposit_tree* tree, size_t m, const uint64_t* counts, uint8_t* roots32);
+int bls381_deposit_tree_roots_device(bls381_deposit_tree* tree, size_t m, const uint64_t* h_counts, uint8_t* d_roots32,
+                                     void* stream);
+size_t bls381_deposit_tree_proofs_workspace_size(uint32_t depth);
+int bls381_deposit_tree_proofs(bls381_deposit_tree* tree, uint64_t k, size_t n_idx, const uint64_t* indices,
+                               uint8_t* proofs, size_t proof_stride, uint8_t root[32]);
+int bls381_deposit_tree_proofs_device(bls381_deposit_tree* tree, uint64_t k, size_t n_idx, const uint64_t* d_indices,
+                                      uint8_t* d_proofs, size_t proof_stride, uint8_t* d_root32, void* d_workspace,
+                                      void* stream);
+size_t bls381_deposit_tree_deposits_workspace_size(size_t n);
+int bls381_deposit_tree_deposits(bls381_deposit_tree* tree, uint64_t k, uint64_t first_index, size_t n,
+                                 const uint8_t* deposit_data, uint8_t* deposits);
+int bls381_deposit_tree_deposits_device(bls381_deposit_tree* tree, uint64_t k, uint64_t first_index, size_t n,
+                                        const uint8_t* d_deposit_data, uint8_t* d_deposits, void* d_workspace,
+                                        void* stream);
+
 /* ---- committees: the producer of the grouped verify's d_entries ---------- */
 /* get_shuffled_index (0_beacon-chain.md:860-882) for positions first .. first+count-1 of a list of
  * index_count: out[k] = shuffled(first+k), or indices[shuffled(first+k)] when indices != NULL
