@@ -153,6 +153,20 @@ _SIGS = {
                                                 _u8p, _u8p, _u8p, ctypes.c_size_t]),
     "bls381_attesting_entries_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p,
                                                        ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p, _u8p]),
+    "bls381_active_indices_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_active_indices": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64, _u8p,
+                                             ctypes.c_size_t, _u8p, _u8p, _u8p]),
+    "bls381_active_indices_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64, _u8p,
+                                                    ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_active_index_root_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_active_index_root": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p]),
+    "bls381_active_index_root_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_proposer_indices_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_proposer_indices": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p, ctypes.c_size_t,
+                                               ctypes.c_size_t, _u8p, ctypes.c_uint64, ctypes.c_uint64, _u8p]),
+    "bls381_proposer_indices_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p,
+                                                      ctypes.c_size_t, ctypes.c_size_t, _u8p, ctypes.c_uint64,
+                                                      ctypes.c_uint64, _u8p, _u8p, _u8p]),
     "bls381_registry_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     "bls381_registry_destroy": (None, [ctypes.c_void_p]),
     "bls381_registry_size": (ctypes.c_size_t, [ctypes.c_void_p]),

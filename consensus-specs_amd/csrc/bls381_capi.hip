@@ -2709,6 +2709,286 @@ int bls381_attesting_entries(size_t n_att, const uint32_t* committee_off, const 
   });
 }
 
+// ---- epoch context: active indices, their root, proposers (bls381_epoch.hpp)
+static bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+// a field of n entries whose span does not overflow
+static bool field_ok(size_t n, size_t stride) { return stride >= 8 && (n < 2 || stride <= (SIZE_MAX - 8) / (n - 1)); }
+struct ActiveWs {
+  uint64_t *ballots, *tile_balance;
+  uint32_t *tile_count, *tile_offset;
+};
+static ActiveWs carve_active(Bump& b, size_t n) {
+  const size_t tiles = active_tiles(n);
+  ActiveWs w;
+  w.ballots = b.take<uint64_t>(tiles * ACTIVE_TILE_BALLOTS);
+  w.tile_balance = b.take<uint64_t>(tiles);
+  w.tile_count = b.take<uint32_t>(tiles);
+  w.tile_offset = b.take<uint32_t>(tiles);
+  return w;
+}
+size_t bls381_active_indices_workspace_size(size_t n) {
+  if ((uint64_t)n > 0xFFFFFFFFull) return 0;
+  return carved_bytes([&](Bump& b) { carve_active(b, n); });
+}
+
+int bls381_active_indices_device(size_t n, const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch, size_t stride,
+                                 uint64_t epoch, const uint8_t* d_effective_balance, size_t balance_stride,
+                                 uint32_t* d_indices, uint64_t* d_count_and_total, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || (d_effective_balance && !field_ok(n, balance_stride)) ||
+        !d_count_and_total || !aligned8(d_count_and_total) || !aligned4(d_indices))
+      return BLS381_EARG;
+    if (n && (!d_activation_epoch || !d_exit_epoch || !d_indices || !d_workspace)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+      HIPC(hipMemsetAsync(d_count_and_total, 0, 16, s));
+      return 0;
+    }
+    Bump b(d_workspace, bls381_active_indices_workspace_size(n));
+    const ActiveWs w = carve_active(b, n);
+    const size_t tiles = active_tiles(n);
+    const int has_balance = d_effective_balance ? 1 : 0;
+    const u64_field act = make_u64_field(d_activation_epoch, stride), ext = make_u64_field(d_exit_epoch, stride);
+    const u64_field bal = has_balance ? make_u64_field(d_effective_balance, balance_stride) : act;
+    const dim3 blk(EPOCH_BLOCK);
+    LAUNCH("active_count", s, dim3((unsigned)tiles), blk, k_active_count, (uint64_t)n, act, ext, epoch, has_balance, bal,
+           w.ballots, w.tile_count, w.tile_balance);
+    LAUNCH("active_scan", s, dim3(1), blk, k_active_scan, tiles, (const uint32_t*)w.tile_count,
+           (const uint64_t*)w.tile_balance, w.tile_offset, d_count_and_total);
+    LAUNCH("active_scatter", s, dim3((unsigned)tiles), blk, k_active_scatter, (const uint64_t*)w.ballots,
+           (const uint32_t*)w.tile_offset, d_indices);
+    return 0;
+  });
+}
+
+// Host fields to the device: fields that interleave in one buffer of records (the same stride, bases
+// less than a stride apart) travel as one copy of their union, any other field as its own span.
+// Each copy keeps its base's offset within 8 bytes, so the device loads are as wide as the
+// host's would be.
+namespace {
+struct HostFields {
+  static constexpr int MAXF = 3;
+  const uint8_t* h[MAXF];
+  size_t stride[MAXF];
+  int nf = 0, group[MAXF];           // group: the copy a field travels in
+  const uint8_t* lo[MAXF];           // per copy: host range
+  size_t bytes[MAXF];
+  uint8_t* d[MAXF];                  // per copy: device block (bytes + 8)
+  int ncopies = 0;
+  void add(const uint8_t* p, size_t st) { h[nf] = p; stride[nf] = st; ++nf; }
+  void plan(size_t n) {
+    for (int f = 0; f < nf; ++f) {
+      group[f] = -1;
+      for (int g = 0; g < f && group[f] < 0; ++g) {
+        const uintptr_t a = (uintptr_t)h[f], o = (uintptr_t)h[g];
+        if (stride[f] == stride[g] && stride[f] > 8 && (a > o ? a - o : o - a) < stride[f]) group[f] = group[g];
+      }
+      if (group[f] < 0) {
+        group[f] = ncopies;
+        lo[ncopies] = h[f];
+        bytes[ncopies] = 0;
+        ++ncopies;
+      }
+    }
+    for (int f = 0; f < nf; ++f) {
+      const int g = group[f];
+      const uint8_t* end = std::max(lo[g] + bytes[g], h[f] + field_span(n, stride[f]));
+      lo[g] = std::min(lo[g], h[f]);
+      bytes[g] = (size_t)(end - lo[g]);
+    }
+  }
+  void carve(Bump& b) {
+    for (int g = 0; g < ncopies; ++g) d[g] = b.take<uint8_t>(bytes[g] + 8);
+  }
+  uint8_t* dev_lo(int g) const { return d[g] + ((uintptr_t)lo[g] & 7u); }
+  const uint8_t* dev(int f) const { return dev_lo(group[f]) + (h[f] - lo[group[f]]); }
+};
+}  // namespace
+
+int bls381_active_indices(size_t n, const uint8_t* activation_epoch, const uint8_t* exit_epoch, size_t stride,
+                          uint64_t epoch, const uint8_t* effective_balance, size_t balance_stride,
+                          uint32_t* indices_out, uint64_t* count_out, uint64_t* total_balance_out) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || (effective_balance && !field_ok(n, balance_stride)) ||
+        !count_out)
+      return BLS381_EARG;
+    if (n && (!activation_epoch || !exit_epoch || !indices_out)) return BLS381_EARG;
+    *count_out = 0;
+    if (total_balance_out) *total_balance_out = 0;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(activation_epoch, stride);
+    hf.add(exit_epoch, stride);
+    if (effective_balance) hf.add(effective_balance, balance_stride);
+    hf.plan(n);
+    const size_t wsb = bls381_active_indices_workspace_size(n);
+    uint32_t* d_idx;
+    uint64_t* d_out;
+    uint8_t* d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_idx = b.take<uint32_t>(n);
+      d_out = b.take<uint64_t>(2);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(bls381_active_indices_device(n, hf.dev(0), hf.dev(1), stride, epoch, effective_balance ? hf.dev(2) : nullptr,
+                                     balance_stride, d_idx, d_out, d_ws, hc.s));
+    uint64_t out[2];
+    TRY(hc.download(out, d_out, 16));
+    HIPC(hipStreamSynchronize(hc.s));   // the count decides how much of the list comes back
+    TRY(hc.download(indices_out, d_idx, 4 * (size_t)out[0]));
+    TRY(hc.finish());
+    *count_out = out[0];
+    if (total_balance_out) *total_balance_out = out[1];
+    return 0;
+  });
+}
+
+struct IndexRootWs {
+  uint64_t* chunks;
+  uint8_t* merkle;
+};
+static IndexRootWs carve_index_root(Bump& b, size_t n) {
+  const size_t chunks = index_chunk_count(n);
+  IndexRootWs w;
+  w.chunks = b.take<uint64_t>(4 * chunks);
+  w.merkle = b.take<uint8_t>(bls381_merkle_root_workspace_size(chunks, 0, merkle_chunk_depth(chunks)));
+  return w;
+}
+size_t bls381_active_index_root_workspace_size(size_t n) {
+  if ((uint64_t)n > 0xFFFFFFFFull) return 0;
+  return carved_bytes([&](Bump& b) { carve_index_root(b, n); });
+}
+
+int bls381_active_index_root_device(size_t n, const uint32_t* d_indices, uint8_t* d_root32, void* d_workspace,
+                                    void* stream) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !d_root32 || !d_workspace || (n && !d_indices) || !aligned4(d_indices))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_active_index_root_workspace_size(n));
+    const IndexRootWs w = carve_index_root(b, n);
+    const size_t chunks = index_chunk_count(n);
+    LAUNCH("index_chunks", s, dim3(grid_for(4 * chunks, EPOCH_BLOCK)), dim3(EPOCH_BLOCK), k_index_chunks, n, d_indices,
+           w.chunks);
+    // n == 0: no chunk, depth 0, so the root is mix_in_length(zero chunk, 0)
+    return bls381_merkle_root_device(chunks, (const uint8_t*)w.chunks, 0, merkle_chunk_depth(chunks), 1, n, d_root32,
+                                     w.merkle, stream);
+  });
+}
+
+int bls381_active_index_root(size_t n, const uint32_t* indices, uint8_t root[32]) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !root || (n && !indices)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_active_index_root_workspace_size(n);
+    uint32_t* d_idx;
+    uint8_t *d_root, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_idx = b.take<uint32_t>(n);
+      d_root = b.take<uint8_t>(32);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_idx, indices, 4 * n));
+    TRY(bls381_active_index_root_device(n, d_idx, d_root, d_ws, hc.s));
+    TRY(hc.download(root, d_root, 32));
+    return hc.finish();
+  });
+}
+
+size_t bls381_proposer_indices_workspace_size(size_t n_slots) {
+  if (n_slots > (size_t)INT32_MAX) return 0;
+  return carved_bytes([&](Bump& b) { b.take<proposer_slot>(n_slots); });
+}
+static bool proposer_args_ok(size_t n_slots, const uint32_t* off, const uint32_t* len, const void* shuffled,
+                             size_t n_shuffled, const void* balance, size_t balance_stride, size_t n_validators,
+                             const uint8_t* seed, uint64_t max_effective_balance, const void* out) {
+  if (n_slots > (size_t)INT32_MAX || (uint64_t)n_validators > 0xFFFFFFFFull || !field_ok(n_validators, balance_stride) ||
+      max_effective_balance == 0 || max_effective_balance >= PROPOSER_BALANCE_LIMIT)
+    return false;
+  if (n_slots == 0) return true;
+  if (!off || !len || !shuffled || !seed || !out || (n_validators && !balance)) return false;
+  for (size_t k = 0; k < n_slots; ++k)
+    if (len[k] == 0 || (uint64_t)off[k] + len[k] > n_shuffled) return false;
+  return true;
+}
+
+int bls381_proposer_indices_device(size_t n_slots, const uint32_t* h_committee_off, const uint32_t* h_committee_len,
+                                   const uint32_t* d_shuffled, size_t n_shuffled, const uint8_t* d_effective_balance,
+                                   size_t balance_stride, size_t n_validators, const uint8_t seed[32], uint64_t epoch,
+                                   uint64_t max_effective_balance, uint32_t* d_proposer_out, void* d_workspace,
+                                   void* stream) {
+  return guarded([&]() -> int {
+    if (!proposer_args_ok(n_slots, h_committee_off, h_committee_len, d_shuffled, n_shuffled, d_effective_balance,
+                          balance_stride, n_validators, seed, max_effective_balance, d_proposer_out) ||
+        !aligned4(d_shuffled) || !aligned4(d_proposer_out) || (n_slots && !d_workspace))
+      return BLS381_EARG;
+    if (n_slots == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_proposer_indices_workspace_size(n_slots));
+    proposer_slot* d_slots = b.take<proposer_slot>(n_slots);
+    std::vector<proposer_slot> slots(n_slots);
+    for (size_t k = 0; k < n_slots; ++k)
+      slots[k] = proposer_slot{h_committee_off[k], h_committee_len[k], (uint32_t)(epoch % h_committee_len[k])};
+    Held<std::vector<proposer_slot>> hold(c->keep, s, std::move(slots));
+    HIPC(hipMemcpyAsync(d_slots, hold->data(), n_slots * sizeof(proposer_slot), hipMemcpyHostToDevice, s));
+    LAUNCH("proposers", s, dim3((unsigned)n_slots), dim3(EPOCH_BLOCK), k_proposers, (const proposer_slot*)d_slots,
+           d_shuffled, make_u64_field(d_effective_balance, balance_stride), (uint64_t)n_validators,
+           shuffle_seed_from_bytes(seed), max_effective_balance, d_proposer_out);
+    return 0;
+  });
+}
+
+int bls381_proposer_indices(size_t n_slots, const uint32_t* committee_off, const uint32_t* committee_len,
+                            const uint32_t* shuffled, size_t n_shuffled, const uint8_t* effective_balance,
+                            size_t balance_stride, size_t n_validators, const uint8_t seed[32], uint64_t epoch,
+                            uint64_t max_effective_balance, uint32_t* proposer_out) {
+  return guarded([&]() -> int {
+    if (!proposer_args_ok(n_slots, committee_off, committee_len, shuffled, n_shuffled, effective_balance, balance_stride,
+                          n_validators, seed, max_effective_balance, proposer_out))
+      return BLS381_EARG;
+    if (n_slots == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_proposer_indices_workspace_size(n_slots);
+    const size_t span = field_span(n_validators, balance_stride);
+    uint32_t *d_sh, *d_out;
+    uint8_t *d_bal, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_sh = b.take<uint32_t>(n_shuffled);
+      d_bal = b.take<uint8_t>(span + 8);
+      d_out = b.take<uint32_t>(n_slots);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    d_bal += (uintptr_t)effective_balance & 7u;   // the host base's offset within 8 bytes
+    TRY(hc.upload(d_sh, shuffled, 4 * n_shuffled));
+    TRY(hc.upload(d_bal, effective_balance, span));
+    TRY(bls381_proposer_indices_device(n_slots, committee_off, committee_len, d_sh, n_shuffled, d_bal, balance_stride,
+                                       n_validators, seed, epoch, max_effective_balance, d_out, d_ws, hc.s));
+    TRY(hc.download(proposer_out, d_out, 4 * n_slots));
+    return hc.finish();
+  });
+}
+
 }  // extern "C"
 
 // ---- multi-GPU over RCCL: one process per GPU, a communicator

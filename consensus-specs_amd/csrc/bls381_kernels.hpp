@@ -15,6 +15,7 @@
 #include "bls381_merkle.hpp"
 #include "bls381_deptree.hpp"
 #include "bls381_shuffle.hpp"
+#include "bls381_epoch.hpp"
 
 namespace bls381 {
 
@@ -2059,6 +2060,149 @@ __global__ void __launch_bounds__(ATT_BLOCK) k_attesting_entries(const att_desc*
   if (d.n1)
     attesting_group(buf, cnt, threadIdx.x, ATT_BLOCK, wg_sync{}, committee, d.committee_len, agg, cust, 1, d.n1,
                     entries + d.out_off + d.n0);
+}
+
+// ------------------------------ epoch context: active indices, index chunks, proposers (§7f) --
+// (the tile geometry, the field loads and the proposer's arithmetic: bls381_epoch.hpp)
+// Tile blockIdx.x: its 32 ballots, its count and (has_balance) its active balance sum.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_active_count(uint64_t n, u64_field activation, u64_field exit_,
+                                                              uint64_t epoch, int has_balance, u64_field balance,
+                                                              uint64_t* __restrict__ ballots,
+                                                              uint32_t* __restrict__ tile_count,
+                                                              uint64_t* __restrict__ tile_balance) {
+  __shared__ uint32_t wave_count[EPOCH_BLOCK / 64];
+  __shared__ uint64_t lane_sum[EPOCH_BLOCK];
+  const size_t tile = blockIdx.x;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  uint32_t count = 0;   // the same on every lane of a wave
+  uint64_t sum = 0;
+  for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k) {
+    const uint64_t i = active_item(tile, k, tid);
+    const bool a = i < n && validator_active(activation, exit_, epoch, (size_t)i);
+    const uint64_t m = __ballot(a);
+    if ((tid & 63u) == 0) ballots[tile * ACTIVE_TILE_BALLOTS + 4 * k + wave] = m;
+    count += (uint32_t)__popcll(m);
+    if (a && has_balance) sum += field_load(balance, (size_t)i);
+  }
+  if ((tid & 63u) == 0) wave_count[wave] = count;
+  if (has_balance) {   // the same for the whole launch
+    lane_sum[tid] = sum;
+    for (uint32_t s = EPOCH_BLOCK / 2; s > 0; s >>= 1) {
+      __syncthreads();
+      if (tid < s) lane_sum[tid] += lane_sum[tid + s];
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    tile_count[tile] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    tile_balance[tile] = has_balance ? lane_sum[0] : 0;
+  }
+}
+
+// One workgroup: tile_offset = exclusive scan of tile_count, 256 tiles a round; out[0] = the count,
+// out[1] = the balance sum.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_active_scan(size_t tiles, const uint32_t* __restrict__ tile_count,
+                                                             const uint64_t* __restrict__ tile_balance,
+                                                             uint32_t* __restrict__ tile_offset,
+                                                             uint64_t* __restrict__ out) {
+  __shared__ uint32_t scan[EPOCH_BLOCK];
+  __shared__ uint64_t lane_sum[EPOCH_BLOCK];
+  const uint32_t tid = threadIdx.x;
+  const size_t rounds = (tiles + EPOCH_BLOCK - 1) / EPOCH_BLOCK;
+  uint64_t carry = 0, sum = 0;
+  for (size_t r = 0; r < rounds; ++r) {
+    const size_t j = r * EPOCH_BLOCK + tid;
+    const uint32_t c = j < tiles ? tile_count[j] : 0;
+    if (j < tiles) sum += tile_balance[j];
+    scan[tid] = c;
+    __syncthreads();
+    for (uint32_t d = 1; d < EPOCH_BLOCK; d <<= 1) {   // inclusive scan in place
+      const uint32_t v = tid >= d ? scan[tid - d] : 0;
+      __syncthreads();
+      scan[tid] += v;
+      __syncthreads();
+    }
+    if (j < tiles) tile_offset[j] = (uint32_t)(carry + scan[tid] - c);
+    carry += scan[EPOCH_BLOCK - 1];
+    __syncthreads();   // scan is rewritten next round
+  }
+  lane_sum[tid] = sum;
+  for (uint32_t s = EPOCH_BLOCK / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (tid < s) lane_sum[tid] += lane_sum[tid + s];
+  }
+  if (tid == 0) {
+    out[0] = carry;
+    out[1] = lane_sum[0];
+  }
+}
+
+// Tile blockIdx.x: its active validators to indices, ascending, from the ballots of k_active_count.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_active_scatter(const uint64_t* __restrict__ ballots,
+                                                                const uint32_t* __restrict__ tile_offset,
+                                                                uint32_t* __restrict__ indices) {
+  __shared__ uint32_t before[ACTIVE_TILE_BALLOTS];
+  const size_t tile = blockIdx.x;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  const uint64_t* mine = ballots + tile * ACTIVE_TILE_BALLOTS;
+  if (tid == 0) {
+    uint32_t at = 0;
+    for (uint32_t b = 0; b < ACTIVE_TILE_BALLOTS; ++b) {
+      before[b] = at;
+      at += (uint32_t)__popcll(mine[b]);
+    }
+  }
+  __syncthreads();
+  const uint32_t base = tile_offset[tile];
+  for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k) {
+    const uint64_t m = mine[4 * k + wave];
+    if ((m >> (tid & 63u)) & 1u) {
+      // a set bit is a validator below n (k_active_count), and its position is below the count
+      const uint32_t lanes_before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      indices[base + before[4 * k + wave] + lanes_before] = (uint32_t)active_item(tile, k, tid);
+    }
+  }
+}
+
+// the packed chunks of List[uint64] over n uint32 indices: word t of 4 * ceil(n / 4)
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_index_chunks(size_t n, const uint32_t* __restrict__ indices,
+                                                              uint64_t* __restrict__ chunks) {
+  const size_t t = (size_t)blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (t >= 4 * index_chunk_count(n)) return;
+  chunks[t] = index_chunk_word(indices, n, t);
+}
+
+// get_beacon_proposer_index for slot blockIdx.x: windows of 256 tries, the lowest accepting one wins
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_proposers(const proposer_slot* __restrict__ slots,
+                                                           const uint32_t* __restrict__ shuffled, u64_field balance,
+                                                           uint64_t n_validators, shuffle_seed seed,
+                                                           uint64_t max_effective_balance,
+                                                           uint32_t* __restrict__ proposer) {
+  __shared__ uint32_t digest[PROPOSER_WINDOW / 32][8];
+  __shared__ uint64_t verdict[EPOCH_BLOCK / 64];
+  const proposer_slot sl = slots[blockIdx.x];
+  const uint32_t* committee = shuffled + sl.off;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  for (uint32_t w = 0; w < PROPOSER_MAX_TRIES / PROPOSER_WINDOW; ++w) {
+    const uint32_t i = w * PROPOSER_WINDOW + tid;
+    if ((tid & 31u) == 0) proposer_digest(digest[tid >> 5], seed, i >> 5);
+    __syncthreads();
+    uint32_t candidate;
+    const int v = proposer_try(committee, sl, i, proposer_digest_byte(digest[tid >> 5], i & 31u), balance, n_validators,
+                               max_effective_balance, &candidate);
+    const uint64_t m = __ballot(v != PROPOSER_REJECT);
+    if ((tid & 63u) == 0) verdict[wave] = m;
+    __syncthreads();
+    // the first wave with a set bit holds the lowest try (lanes are in try order)
+    uint32_t first = EPOCH_BLOCK;
+    for (uint32_t x = EPOCH_BLOCK / 64; x-- > 0;)
+      if (verdict[x]) first = 64 * x + (uint32_t)__builtin_ctzll(verdict[x]);
+    if (first < EPOCH_BLOCK) {   // the same on every lane
+      if (tid == first) proposer[blockIdx.x] = v == PROPOSER_ACCEPT ? candidate : PROPOSER_NONE;
+      return;
+    }
+  }
+  if (tid == 0) proposer[blockIdx.x] = PROPOSER_NONE;
 }
 
 }  // namespace bls381

@@ -21,6 +21,7 @@
 #include "bls381_pairing.hpp"
 #include "bls381_plan.hpp"
 #include "bls381_shuffle.hpp"
+#include "bls381_epoch.hpp"
 #include "bls381_ssz.hpp"
 #include "bls381_merkle.hpp"
 #include "bls381_deptree.hpp"
@@ -891,6 +892,109 @@ int hc_attesting_groups(const uint32_t* committee, uint32_t committee_len, const
   if (n_out[0]) attesting_group(buf.data(), cnt.data(), 0u, 1u, no_sync, committee, committee_len, agg, cust, 0, n_out[0], out0);
   if (n_out[1]) attesting_group(buf.data(), cnt.data(), 0u, 1u, no_sync, committee, committee_len, agg, cust, 1, n_out[1], out1);
   return 1;
+}
+
+// ---- epoch context (bls381_epoch.hpp): the three phases of the active-index compaction in the
+// kernels' own tile geometry, the packed index chunks and one slot's proposer search
+// get_active_validator_indices over fields at base + i * stride, on `threads` host threads:
+// indices_out (room for n), out2[0] = count, out2[1] = the active balance sum (0 without
+// balances).  0, or -1 for arguments the engine rejects.
+int hc_active_indices(uint64_t n, const uint8_t* activation, const uint8_t* exit_, size_t stride, uint64_t epoch,
+                      const uint8_t* balance, size_t balance_stride, int threads, uint32_t* indices_out, uint64_t* out2) {
+  if (n > 0xFFFFFFFFull || stride < 8 || (balance && balance_stride < 8) || threads < 1) return -1;
+  out2[0] = out2[1] = 0;
+  if (n == 0) return 0;
+  const u64_field act = make_u64_field(activation, stride), ext = make_u64_field(exit_, stride);
+  const u64_field bal = balance ? make_u64_field(balance, balance_stride) : act;
+  const size_t tiles = active_tiles(n);
+  std::vector<uint64_t> ballots(tiles * ACTIVE_TILE_BALLOTS), tile_balance(tiles);
+  std::vector<uint32_t> tile_count(tiles), tile_offset(tiles);
+  auto run = [&](auto body) {
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; ++t) pool.emplace_back([=] { body((size_t)t); });
+    for (auto& th : pool) th.join();
+  };
+  run([&](size_t t) {   // k_active_count
+    for (size_t tile = t; tile < tiles; tile += (size_t)threads) {
+      uint32_t count = 0;
+      uint64_t sum = 0;
+      for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k)
+        for (uint32_t wave = 0; wave < EPOCH_BLOCK / 64; ++wave) {
+          uint64_t m = 0;
+          for (uint32_t lane = 0; lane < 64; ++lane) {
+            const uint64_t i = active_item(tile, k, 64 * wave + lane);
+            if (i < n && validator_active(act, ext, epoch, (size_t)i)) {
+              m |= (uint64_t)1 << lane;
+              if (balance) sum += field_load(bal, (size_t)i);
+            }
+          }
+          ballots[tile * ACTIVE_TILE_BALLOTS + 4 * k + wave] = m;
+          count += (uint32_t)__builtin_popcountll(m);
+        }
+      tile_count[tile] = count;
+      tile_balance[tile] = sum;
+    }
+  });
+  uint64_t carry = 0, total = 0;   // k_active_scan
+  for (size_t j = 0; j < tiles; ++j) {
+    tile_offset[j] = (uint32_t)carry;
+    carry += tile_count[j];
+    total += tile_balance[j];
+  }
+  out2[0] = carry;
+  out2[1] = total;
+  run([&](size_t t) {   // k_active_scatter
+    for (size_t tile = t; tile < tiles; tile += (size_t)threads) {
+      uint32_t before = 0;
+      for (uint32_t b = 0; b < ACTIVE_TILE_BALLOTS; ++b) {
+        const uint64_t m = ballots[tile * ACTIVE_TILE_BALLOTS + b];
+        for (uint32_t lane = 0; lane < 64; ++lane)
+          if ((m >> lane) & 1u)
+            indices_out[tile_offset[tile] + before + ballot_before(m, lane)] =
+                (uint32_t)active_item(tile, b / 4, 64 * (b % 4) + lane);
+        before += (uint32_t)__builtin_popcountll(m);
+      }
+    }
+  });
+  return 0;
+}
+
+// the packed chunks of List[uint64] over n uint32 indices: 4 * ceil(n / 4) words to chunks_out
+void hc_index_chunks(uint64_t n, const uint32_t* indices, uint64_t* chunks_out) {
+  for (size_t t = 0; t < 4 * index_chunk_count(n); ++t) chunks_out[t] = index_chunk_word(indices, (size_t)n, t);
+}
+
+// SHA-256(seed || u64le(q)) as 32 bytes (proposer_digest)
+void hc_proposer_digest(const uint8_t* seed32, uint64_t q, uint8_t* out32) {
+  uint32_t d[8];
+  proposer_digest(d, shuffle_seed_from_bytes(seed32), q);
+  for (uint32_t j = 0; j < 32; ++j) out32[j] = (uint8_t)proposer_digest_byte(d, j);
+}
+
+// get_beacon_proposer_index over one committee, try by try up to max_tries (the engine's cap is
+// PROPOSER_MAX_TRIES): the proposer, or 0xFFFFFFFF at the cap, for an out-of-range candidate or
+// for arguments the engine rejects; *tries_out = the try that ended the search (max_tries at the cap).
+uint32_t hc_proposer_index(const uint32_t* committee, uint32_t committee_len, uint64_t epoch, const uint8_t* balance,
+                           size_t balance_stride, uint64_t n_validators, const uint8_t* seed32,
+                           uint64_t max_effective_balance, uint32_t max_tries, uint32_t* tries_out) {
+  *tries_out = 0;
+  if (committee_len == 0 || balance_stride < 8 || max_effective_balance == 0 ||
+      max_effective_balance >= PROPOSER_BALANCE_LIMIT || max_tries > PROPOSER_MAX_TRIES)
+    return PROPOSER_NONE;
+  const shuffle_seed sd = shuffle_seed_from_bytes(seed32);
+  const u64_field bal = make_u64_field(balance, balance_stride);
+  const proposer_slot sl{0, committee_len, (uint32_t)(epoch % committee_len)};
+  uint32_t d[8];
+  for (uint32_t i = 0; i < max_tries; ++i) {
+    if (i % 32 == 0) proposer_digest(d, sd, i / 32);
+    uint32_t candidate;
+    const int v = proposer_try(committee, sl, i, proposer_digest_byte(d, i % 32), bal, n_validators,
+                               max_effective_balance, &candidate);
+    *tries_out = i;
+    if (v != PROPOSER_REJECT) return v == PROPOSER_ACCEPT ? candidate : PROPOSER_NONE;
+  }
+  *tries_out = max_tries;
+  return PROPOSER_NONE;
 }
 
 #if defined(BLS_COUNT_OPS)

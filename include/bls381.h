@@ -591,6 +591,72 @@ int bls381_attesting_entries_device(size_t n_att, const uint32_t* h_committee_of
                                     uint32_t* h_group_key_off, uint8_t* h_ok, uint32_t* d_entries, size_t entries_cap,
                                     void* d_workspace, void* stream);
 
+/* ---- epoch context: active indices, their root and the proposers ---------- */
+/* What the shuffle consumes, made where the validator records already are.  A validator field is
+ * a little-endian uint64 at base + i * stride bytes: stride 8 is a plain array; stride 121 with
+ * base = records + 88 / 96 / 113 is activation_epoch / exit_epoch / effective_balance of the
+ * serialized Validator records (0_beacon-chain.md:284-298) that bls381_ssz_list_root_device hashes,
+ * so one buffer of records serves the registry root and the epoch context.  Loads are 8 bytes wide
+ * when base and stride are multiples of 8 and byte-wise otherwise, and none passes
+ * base + (n - 1) * stride + 8.
+ *
+ * bls381_active_indices: get_active_validator_indices (:680-684) over n validators: the
+ * ascending list of the i with activation_epoch[i] <= epoch < exit_epoch[i] (unsigned 64-bit:
+ * FAR_FUTURE_EPOCH is 2^64 - 1) as uint32, their count and, when effective_balance != NULL, the
+ * sum of their effective balances (else 0): get_total_balance of the active set without its floor
+ * of 1.  The sum is 64-bit: it is exact while n * max balance < 2^64 and wraps above.  Entries of
+ * the output past the count are not written.  The device form writes d_count_and_total[0] = count,
+ * [1] = sum; d_indices has room for n entries.
+ * Chaining: bls381_shuffle_device takes index_count as a host scalar, so a caller that feeds it
+ * this list reads d_count_and_total[0] once per epoch -- the only host read of the chain
+ * records -> active indices -> index root -> (seed on the host, 96 bytes) -> shuffle -> entries.
+ *
+ * bls381_active_index_root: hash_tree_root of the list as List[uint64] (:1545, an input of
+ * generate_seed, :807-816): four indices per 32-byte chunk, the last chunk zero-padded, the tree
+ * of depth ceil(log2(ceil(n / 4))) and mix_in_length(n).  n == 0 gives mix_in_length(zero chunk, 0).
+ *
+ * bls381_proposer_indices: get_beacon_proposer_index (:822-840) for n_slots slots at once.  Slot
+ * k's first committee is shuffled[committee_off[k] .. + committee_len[k]) (as in
+ * bls381_attesting_entries; with committees_per_slot committees a slot, committee
+ * committees_per_slot * k of the epoch).  Try i looks at candidate = committee[(epoch + i) % len],
+ * random_byte = SHA-256(seed || u64le(i / 32))[i % 32], and accepts when
+ * effective_balance * 255 >= max_effective_balance * random_byte (the balance clamped to
+ * max_effective_balance first, which leaves the verdict as it is); proposer_out[k] is the first
+ * accepted candidate.  seed and the committee arrays are host memory in both forms.
+ * Divergences: the search stops after 2^20 tries with 0xFFFFFFFF (a committee whose balances are
+ * all 0 still accepts a try with probability 1/256 and reaches the cap with probability below
+ * 2^-5900), and a try whose candidate is not below n_validators ends its slot with 0xFFFFFFFF
+ * without reading a balance.
+ *
+ * BLS381_EARG: n or n_validators above 2^32 - 1, n_slots above 2^31 - 1, a stride below 8, a NULL
+ * argument that is needed (fields, outputs and the workspace when the count of items is not 0;
+ * count_out / d_count_and_total and the root always), d_indices / d_shuffled / d_proposer_out not
+ * 4-byte or d_count_and_total not 8-byte aligned, a committee of length 0 or outside n_shuffled,
+ * max_effective_balance of 0 or at least 2^56.  n == 0 / n_slots == 0 is BLS381_OK and runs no
+ * kernel (the count is written as 0).  The device forms are queued on `stream`, not synchronised;
+ * workspaces hold bls381_*_workspace_size bytes (0 for arguments the call rejects). */
+size_t bls381_active_indices_workspace_size(size_t n);
+int bls381_active_indices(size_t n, const uint8_t* activation_epoch, const uint8_t* exit_epoch, size_t stride,
+                          uint64_t epoch, const uint8_t* effective_balance, size_t balance_stride,
+                          uint32_t* indices_out, uint64_t* count_out, uint64_t* total_balance_out);
+int bls381_active_indices_device(size_t n, const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch, size_t stride,
+                                 uint64_t epoch, const uint8_t* d_effective_balance, size_t balance_stride,
+                                 uint32_t* d_indices, uint64_t* d_count_and_total, void* d_workspace, void* stream);
+size_t bls381_active_index_root_workspace_size(size_t n);
+int bls381_active_index_root(size_t n, const uint32_t* indices, uint8_t root[32]);
+int bls381_active_index_root_device(size_t n, const uint32_t* d_indices, uint8_t* d_root32, void* d_workspace,
+                                    void* stream);
+size_t bls381_proposer_indices_workspace_size(size_t n_slots);
+int bls381_proposer_indices(size_t n_slots, const uint32_t* committee_off, const uint32_t* committee_len,
+                            const uint32_t* shuffled, size_t n_shuffled, const uint8_t* effective_balance,
+                            size_t balance_stride, size_t n_validators, const uint8_t seed[32], uint64_t epoch,
+                            uint64_t max_effective_balance, uint32_t* proposer_out);
+int bls381_proposer_indices_device(size_t n_slots, const uint32_t* h_committee_off, const uint32_t* h_committee_len,
+                                   const uint32_t* d_shuffled, size_t n_shuffled, const uint8_t* d_effective_balance,
+                                   size_t balance_stride, size_t n_validators, const uint8_t seed[32], uint64_t epoch,
+                                   uint64_t max_effective_balance, uint32_t* d_proposer_out, void* d_workspace,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
