@@ -47,6 +47,21 @@ BLS_INLINE void fp_carry(int32_t (&t)[14]) {
   }
 }
 
+// x as a value the optimizer does not look into (no instruction of its own; the host build needs
+// nothing).  Two uses:
+//   * a lane mask m (all ones or zero): `K & m` stays one v_and_b32 with K as its literal, where the
+//     select between K and 0 that the optimizer makes of it takes a v_mov_b32 for K (VOP2's second
+//     source is a register) and the v_cndmask_b32;
+//   * a clamped value: the multiply after `x > 0 ? x : 0` stays straight-line code, where the
+//     optimizer sinks it into a branch of its own (an exec save and restore around two instructions).
+BLS_INLINE uint32_t fp_opaque(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(x));
+#endif
+  return x;
+}
+BLS_INLINE uint32_t fp_lane_mask(bool c) { return fp_opaque(c ? ~0u : 0u); }
+
 // One reduction per linear combination (DESIGN.md "Arithmetic").  s is a
 // non-negative combination of normalized values -- limbs 0..12 in [0, 2^31 - 8],
 // the top limb >= -2 (a subtracted top limb may exceed the borrowed constant's by
@@ -59,17 +74,19 @@ BLS_INLINE void fp_carry(int32_t (&t)[14]) {
 //   one carry pass the value is in [0, 4q).  A value >= 2q has top limb >= Q2_13;
 //   that (about one lane in 2^14) takes the exact conditional subtraction under a
 //   wave-uniform branch.
+//   The conditional -2q of both paths is an addend of the carry pass (NQ2 = -2q limb-wise mod
+//   2^32), so each limb costs the pass's shift, three-operand add and mask plus one instruction.
 template <int KMAX>
 BLS_INLINE fp_t fp_reduce_lc(const uint32_t (&s)[14]) {
   static_assert(KMAX >= 1 && KMAX <= 8, "value bound");
   int32_t t[14];
   if (KMAX <= 2) {          // k in {0, 1}
-    const uint32_t m = (int32_t)s[13] > (int32_t)Q2_LIMBS[13] ? ~0u : 0u;
+    const uint32_t m = fp_lane_mask((int32_t)s[13] > (int32_t)Q2_LIMBS[13]);
 #pragma unroll
-    for (int i = 0; i < 14; ++i) t[i] = (int32_t)(s[i] - (Q2_LIMBS[i] & m));
+    for (int i = 0; i < 14; ++i) t[i] = (int32_t)(s[i] + (NQ2_LIMBS[i] & m));
   } else {                  // k <= 7: s_i - k q2_i < 2^31 in magnitude
-    const int32_t top = (int32_t)s[13] > 0 ? (int32_t)s[13] : 0;   // < 0: value < 2q, k = 0
-    const uint32_t k = (uint32_t)(((uint64_t)(uint32_t)top * LC_DIV_MAGIC) >> 40);
+    const uint32_t top = fp_opaque((uint32_t)((int32_t)s[13] > 0 ? s[13] : 0u));   // < 0: value < 2q, k = 0
+    const uint32_t k = (uint32_t)(((uint64_t)top * LC_DIV_MAGIC) >> 40);
 #pragma unroll
     for (int i = 0; i < 14; ++i) t[i] = (int32_t)(s[i] + k * NQ2_LIMBS[i]);
   }

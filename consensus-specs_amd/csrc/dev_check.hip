@@ -28,7 +28,8 @@
 //               P_CONJ, P_MUL_XI, P_ADD_MUL_XI, P_SUB2, P_3PM2 (aux: minus), P_MUL_SMALL (aux: k),
 //               P_INV, P_PRED (flag: fp2_is_zero(a) | fp2_eq(a, b) << 1 | pr_both(a0 == b0) << 2),
 //               the fused combinations P_ADD_XI_SUB2, P_SUB2_ADD_XI, P_SUB2_ADD (4 operands each),
-//               P_SUB_SUB_XI, P_SUB_SUB_DBL, P_DBL_SUB2, P_3A_XI_B_M2C, P_2A_B_M3C (3 each)
+//               P_SUB_SUB_XI, P_SUB_SUB_DBL, P_DBL_SUB2, P_3A_XI_B_M2C, P_2A_B_M3C (3 each),
+//               P_ADD, P_SUB, P_DBL (fp_reduce_lc's conditional-subtraction path alone)
 //   pair Fp12   P12_MUL, P12_SQR, P12_CYC_SQR, P12_MUL_BY_LINE, P12_FROB (p = 1, 2, 3), P12_INV,
 //               P_CSQR (cyc_csqr on (g2..g5), aux: count), P12_FINAL_EXP (final_exp, the chain with
 //               the exact fallback), P12_FINAL_EXP_NOFB (final_exp_ct<.., 0>, k_final_exp_verdict's:
@@ -113,7 +114,10 @@ namespace {
   X(P_SUB_SUB_DBL, 2, 2, 3, 1, 0)      \
   X(P_DBL_SUB2, 2, 2, 3, 1, 0)         \
   X(P_3A_XI_B_M2C, 2, 2, 3, 1, 0)      \
-  X(P_2A_B_M3C, 2, 2, 3, 1, 0)
+  X(P_2A_B_M3C, 2, 2, 3, 1, 0)        \
+  X(P_ADD, 2, 2, 2, 1, 0)              \
+  X(P_SUB, 2, 2, 2, 1, 0)              \
+  X(P_DBL, 2, 2, 1, 1, 0)
 
 enum dc_op : int {
 #define X(name, g, gin, nin, nout, pad) name,
@@ -304,15 +308,19 @@ __device__ __forceinline__ void probe(const fp_t* I, uint64_t aux, fp_t* O, uint
   else if constexpr (OP == P_DBL_SUB2) O[0] = fp2_dbl_sub2(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
   else if constexpr (OP == P_3A_XI_B_M2C) O[0] = fp2_3a_xi_b_m2c(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
   else if constexpr (OP == P_2A_B_M3C) O[0] = fp2_2a_b_m3c(pr_make(I[0]), pr_make(I[1]), pr_make(I[2])).v;
+  else if constexpr (OP == P_ADD) O[0] = fp2_add(pr_make(I[0]), pr_make(I[1])).v;
+  else if constexpr (OP == P_SUB) O[0] = fp2_sub(pr_make(I[0]), pr_make(I[1])).v;
+  else if constexpr (OP == P_DBL) O[0] = fp2_dbl(pr_make(I[0])).v;
 }
 
-// one wave per block; L lanes in all (a multiple of 64), the first `live` of them store
-template <int OP>
-__global__ void __launch_bounds__(64) k_probe(const uint32_t* __restrict__ in, const uint64_t* __restrict__ aux,
+// BLOCK lanes per block -- one wave, or for dc_run_wg the product kernels' workgroup of two (KBLOCK);
+// L lanes in all (a multiple of BLOCK), the first `live` of them store
+template <int OP, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_probe(const uint32_t* __restrict__ in, const uint64_t* __restrict__ aux,
                                               uint32_t* __restrict__ out, uint32_t* __restrict__ flag, size_t L,
                                               size_t live) {
   constexpr int NIN = OPS[OP].nin, NOUT = OPS[OP].nout;
-  const size_t lane = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const size_t lane = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   fp_t I[NIN], O[NOUT];
 #pragma unroll
   for (int j = 0; j < NIN; ++j) I[j] = lane_ld(in, L, lane, j);
@@ -325,12 +333,25 @@ __global__ void __launch_bounds__(64) k_probe(const uint32_t* __restrict__ in, c
   ((g_u32*)flag)[lane] = fl;
 }
 
+// the lane-pair probes of at most four operands also exist as one workgroup of KBLOCK lanes
+constexpr bool wg_probe(int op) { return OPS[op].g == 2 && OPS[op].nin <= 4 && OPS[op].nout <= 4; }
+
 template <int OP>
 hipError_t launch(int op, size_t L, size_t live, const uint32_t* in, const uint64_t* aux, uint32_t* out,
-                  uint32_t* flag) {
+                  uint32_t* flag, int block) {
   if constexpr (OP < DC_NOPS) {
-    if (op != OP) return launch<OP + 1>(op, L, live, in, aux, out, flag);
-    hipLaunchKernelGGL(k_probe<OP>, dim3((unsigned)(L / 64)), dim3(64), 0, 0, in, aux, out, flag, L, live);
+    if (op != OP) return launch<OP + 1>(op, L, live, in, aux, out, flag, block);
+    if (block == 64) {
+      hipLaunchKernelGGL((k_probe<OP, 64>), dim3((unsigned)(L / 64)), dim3(64), 0, 0, in, aux, out, flag, L, live);
+    } else {
+      if constexpr (wg_probe(OP)) {
+        if (block != KBLOCK || L % KBLOCK) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_probe<OP, KBLOCK>), dim3((unsigned)(L / KBLOCK)), dim3(KBLOCK), 0, 0, in, aux, out, flag,
+                           L, live);
+      } else {
+        return hipErrorInvalidValue;
+      }
+    }
     return hipGetLastError();
   } else {
     return hipErrorInvalidValue;
@@ -350,11 +371,13 @@ int dc_op_info(int op, int info[4]) {
   return 0;
 }
 
+}  // extern "C"
+namespace {
 // 0 or the HIP error code; host pointers in and out, null stream, nothing left allocated
-int dc_run(int op, size_t n, const uint32_t* in, const uint64_t* aux, uint32_t* out, uint32_t* flag) {
+int run(int op, size_t n, const uint32_t* in, const uint64_t* aux, uint32_t* out, uint32_t* flag, int block) {
   if (op < 0 || op >= DC_NOPS || n == 0 || n > 4096) return (int)hipErrorInvalidValue;
   const op_info& o = OPS[op];
-  const size_t per_wave = 64 / (size_t)o.g;
+  const size_t per_wave = (size_t)block / (size_t)o.g;
   const size_t n_pad = (n + per_wave - 1) / per_wave * per_wave;
   const size_t L = n_pad * o.g, live = n * o.g;
   std::vector<uint32_t> hin((size_t)o.nin * FP_LIMBS * L, 0u), hout((size_t)o.nout * FP_LIMBS * L);
@@ -379,7 +402,7 @@ int dc_run(int op, size_t n, const uint32_t* in, const uint64_t* aux, uint32_t* 
   if (e == hipSuccess) e = hipMalloc(&daux, L * 8);
   if (e == hipSuccess) e = hipMemcpy(din, hin.data(), hin.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(daux, haux.data(), L * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch<0>(op, L, live, din, daux, dout, dflag);
+  if (e == hipSuccess) e = launch<0>(op, L, live, din, daux, dout, dflag, block);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(hout.data(), dout, hout.size() * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(hflag.data(), dflag, L * 4, hipMemcpyDeviceToHost);
@@ -394,6 +417,17 @@ int dc_run(int op, size_t n, const uint32_t* in, const uint64_t* aux, uint32_t* 
           out[((i * o.nout + j) * o.g + l) * FP_LIMBS + k] = hout[(size_t)(j * FP_LIMBS + k) * L + lane];
     }
   return 0;
+}
+}  // namespace
+extern "C" {
+
+int dc_run(int op, size_t n, const uint32_t* in, const uint64_t* aux, uint32_t* out, uint32_t* flag) {
+  return run(op, n, in, aux, out, flag, 64);
+}
+// the same on workgroups of KBLOCK lanes (two waves, the product kernels' shape): the lane-pair probes
+// of at most four operands only, any other op is hipErrorInvalidValue
+int dc_run_wg(int op, size_t n, const uint32_t* in, const uint64_t* aux, uint32_t* out, uint32_t* flag) {
+  return run(op, n, in, aux, out, flag, KBLOCK);
 }
 
 }  // extern "C"
