@@ -1419,8 +1419,7 @@ int bls381_registry_create(size_t capacity, bls381_registry** out) {
   auto* r = new bls381_registry();
   r->device = c->device;
   r->cap = capacity;
-  size_t t = 1;
-  while (t < 2 * capacity) t <<= 1;
+  const size_t t = registry_table_slots(capacity);
   r->tmask = (uint32_t)(t - 1);
   if (hipMalloc(&r->keys, 48 * capacity) != hipSuccess || hipMalloc(&r->aff, 2 * FPW * capacity) != hipSuccess ||
       hipMalloc(&r->st, capacity) != hipSuccess || hipMalloc(&r->table, 4 * t) != hipSuccess ||

@@ -16,6 +16,7 @@
 #include "bls381_deptree.hpp"
 #include "bls381_shuffle.hpp"
 #include "bls381_epoch.hpp"
+#include "bls381_keytable.hpp"
 
 namespace bls381 {
 
@@ -1410,25 +1411,8 @@ __global__ void __launch_bounds__(KBLOCK, BLS_WAVES_PER_EU) k_agg_g1_affine(size
 // Device-resident registry of decoded pubkeys: entry j
 // holds the 48-byte key, its status and its affine point (entry-major, reg_st_g1); an
 // open-addressing table (u32 entry per slot, REG_EMPTY when free, linear
-// probing, power-of-two size) maps key bytes to entries.
-constexpr uint32_t REG_EMPTY = 0xFFFFFFFFu;
-
-// 48 key bytes -> 32-bit hash (all 12 words mixed; the x bytes are uniform)
-__device__ __forceinline__ uint32_t reg_hash(const uint8_t* k) {
-  uint32_t h = 0x9E3779B9u;
-  for (int w = 0; w < 12; ++w) {
-    const uint32_t v = (uint32_t)k[4 * w] | ((uint32_t)k[4 * w + 1] << 8) | ((uint32_t)k[4 * w + 2] << 16) |
-                       ((uint32_t)k[4 * w + 3] << 24);
-    h = (h ^ v) * 0x85EBCA6Bu;
-    h ^= h >> 15;
-  }
-  return h;
-}
-__device__ __forceinline__ bool reg_key_eq(const uint8_t* a, const uint8_t* b) {
-  uint32_t d = 0;
-  for (int i = 0; i < 48; ++i) d |= (uint32_t)(a[i] ^ b[i]);
-  return d == 0;
-}
+// probing, power-of-two size) maps key bytes to entries (REG_EMPTY, reg_hash and reg_key_eq:
+// bls381_keytable.hpp).
 
 // decode keys [first, first + n) in place (status + affine point).  Entries serve calls
 // under either policy: a key is decoded with the lax codec, and one the strict codec

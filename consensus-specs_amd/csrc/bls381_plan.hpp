@@ -510,6 +510,12 @@ inline size_t deposit_table_slots(size_t n) {
   while (t < 2 * n) t <<= 1;
   return t;
 }
+// slots of the registry's key table: the smallest power of two >= 2 capacity
+inline size_t registry_table_slots(size_t capacity) {
+  size_t t = 1;
+  while (t < 2 * capacity) t <<= 1;
+  return t;
+}
 
 // ----------------------------------------------------------- Merkle trees --
 // The plan of tree(leaves[0..n), first, depth) (bls381_merkle.hpp): the tree with 2^depth leaves

@@ -25,6 +25,7 @@
 #include "bls381_ssz.hpp"
 #include "bls381_merkle.hpp"
 #include "bls381_deptree.hpp"
+#include "bls381_keytable.hpp"
 
 // ---- stand-ins for the HIP types and runtime calls that bls381_scope.hpp is written against.
 // Every call appends one line to a log (hc_scope_scenario, at the end of this file, returns it);
@@ -824,6 +825,11 @@ int hc_deptree_plan(uint64_t capacity, uint64_t count, uint64_t n, uint64_t* out
   }
   return 0;
 }
+
+// the pubkey tables' hash (bls381_keytable.hpp) and slot counts (bls381_plan.hpp), as the engine computes them
+uint32_t hc_reg_hash(const uint8_t* key48) { return reg_hash(key48); }
+size_t hc_registry_table_slots(size_t capacity) { return registry_table_slots(capacity); }
+size_t hc_deposit_table_slots(size_t n) { return deposit_table_slots(n); }
 
 // get_shuffled_index (bls381_shuffle.hpp: the direct form, every position hashing its own source
 // block): the shuffled index, or UINT64_MAX for arguments the engine rejects
