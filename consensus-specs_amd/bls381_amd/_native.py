@@ -143,6 +143,27 @@ _SIGS = {
                                                     _u8p, _u8p]),
     "bls381_deposit_tree_deposits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                                            ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_list_tree_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_size_t, _u8p, ctypes.c_uint32,
+                                               ctypes.POINTER(ctypes.c_void_p)]),
+    "bls381_list_tree_destroy": (None, [ctypes.c_void_p]),
+    "bls381_list_tree_count": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bls381_list_tree_capacity": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bls381_list_tree_depth": (ctypes.c_uint32, [ctypes.c_void_p]),
+    "bls381_list_tree_items_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "bls381_list_tree_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, _u8p]),
+    "bls381_list_tree_append_workspace_size": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_size_t]),
+    "bls381_list_tree_append": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p]),
+    "bls381_list_tree_append_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, _u8p]),
+    "bls381_list_tree_update_workspace_size": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_size_t]),
+    "bls381_list_tree_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, ctypes.c_size_t, ctypes.c_size_t,
+                                               _u8p]),
+    "bls381_list_tree_update_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, ctypes.c_size_t,
+                                                      ctypes.c_size_t, _u8p, _u8p, _u8p]),
+    "bls381_list_tree_root": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u8p]),
+    "bls381_list_tree_root_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u8p, _u8p]),
+    "bls381_list_tree_proofs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, _u8p]),
+    "bls381_list_tree_proofs_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t,
+                                                      _u8p, _u8p]),
     "bls381_shuffle_workspace_size": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]),
     "bls381_shuffle": (ctypes.c_int, [ctypes.c_uint64, _u8p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, _u8p,
                                       _u8p]),

@@ -20,6 +20,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <type_traits>
 #include <vector>
 
@@ -2340,6 +2341,325 @@ int bls381_deposit_tree_deposits(bls381_deposit_tree* tree, uint64_t k, uint64_t
     TRY(hc.upload(d_data, deposit_data, DEPOSIT_DATA_BYTES * n));
     TRY(bls381_deposit_tree_deposits_device(tree, k, first_index, n, d_data, d_dep, d_ws, hc.s));
     TRY(hc.download(deposits, d_dep, DEPOSIT_BYTES * n));
+    return hc.finish();
+  });
+}
+
+// ---- SSZ list trees kept on the device (storage and rules: bls381_listtree.hpp)
+// `count` is the host's: it moves when an append is queued.  The root program lives beside the store.
+struct bls381_list_tree {
+  int device = -1;
+  listtree_shape sh{};
+  uint64_t count = 0;
+  uint8_t* store = nullptr;
+  uint32_t* prog = nullptr;   // device copy; null for a packed list
+  uint32_t plen = 0;
+};
+
+int bls381_list_tree_create(size_t capacity, size_t item_size, const uint32_t* prog, uint32_t prog_len,
+                            bls381_list_tree** out) {
+  if (!out) return BLS381_EARG;
+  *out = nullptr;
+  const bool packed = !prog && prog_len == 0;
+  if (!listtree_args_ok(capacity, item_size, packed) || (!packed && !ssz_prog_ok(prog, prog_len, item_size)))
+    return BLS381_EARG;
+  int rc = 0;
+  Ctx* c = get_ctx(&rc);
+  if (!c) return rc;
+  std::unique_ptr<bls381_list_tree> t(new bls381_list_tree());
+  uint64_t bytes = 0;
+  t->device = c->device;
+  t->sh = listtree_make_shape(capacity, (uint32_t)item_size, packed, &bytes);
+  t->plen = prog_len;
+  bool ok = hipMalloc(&t->store, bytes) == hipSuccess && hipMemset(t->store, 0, bytes) == hipSuccess;
+  if (ok && !packed)
+    ok = hipMalloc(&t->prog, 4 * (size_t)prog_len) == hipSuccess &&
+         hipMemcpy(t->prog, prog, 4 * (size_t)prog_len, hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(t->store);
+    (void)hipFree(t->prog);
+    t_err = "list tree allocation failed";
+    return BLS381_EHIP;
+  }
+  *out = t.release();
+  return 0;
+}
+
+void bls381_list_tree_destroy(bls381_list_tree* tree) {
+  if (!tree) return;
+  (void)hipSetDevice(tree->device);
+  (void)hipDeviceSynchronize();   // calls queued on the caller's streams may still read the store
+  (void)hipFree(tree->store);
+  (void)hipFree(tree->prog);
+  delete tree;
+}
+
+static uint64_t listtree_chunks_now(const bls381_list_tree* tree) { return listtree_chunks(tree->sh, tree->count); }
+size_t bls381_list_tree_count(const bls381_list_tree* tree) { return tree ? (size_t)tree->count : 0; }
+size_t bls381_list_tree_capacity(const bls381_list_tree* tree) { return tree ? (size_t)tree->sh.capacity : 0; }
+uint32_t bls381_list_tree_depth(const bls381_list_tree* tree) {
+  return tree ? merkle_chunk_depth(listtree_chunks_now(tree)) : 0;
+}
+const uint8_t* bls381_list_tree_items_device(const bls381_list_tree* tree) { return tree ? tree->store : nullptr; }
+
+static Ctx* listtree_ctx(const bls381_list_tree* tree, int* rc) {
+  Ctx* c = get_ctx(rc);
+  if (c && c->device != tree->device) { t_err = "list tree belongs to another device"; *rc = BLS381_EARG; return nullptr; }
+  return c;
+}
+static bool listtree_fits(const bls381_list_tree* tree, size_t n) { return n <= tree->sh.capacity - tree->count; }
+static uint8_t* listtree_item(bls381_list_tree* tree, uint64_t i) { return tree->store + i * tree->sh.item_size; }
+
+int bls381_list_tree_read(bls381_list_tree* tree, size_t first, size_t n, uint8_t* items_out) {
+  return guarded([&]() -> int {
+    if (!tree || first > tree->count || n > tree->count - first || (n && !items_out)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    TRY(hc.download(items_out, listtree_item(tree, first), n * tree->sh.item_size));
+    return hc.finish();
+  });
+}
+
+// the workspace of an append: the root program's error flag (composite lists)
+size_t bls381_list_tree_append_workspace_size(const bls381_list_tree* tree, size_t n) {
+  if (!tree || n == 0 || !listtree_fits(tree, n) || tree->sh.packed) return 0;
+  return carved_bytes([&](Bump& b) { b.take<int32_t>(1); });
+}
+
+// Queues the re-hash of n items that already sit in the store behind the count -- composite: their
+// roots into row 0; then the passes over the contiguous tiles of their chunks (a packed append
+// that starts inside a chunk takes that chunk along) -- and moves the count.
+static int listtree_append_impl(Ctx* c, bls381_list_tree* tree, size_t n, void* ws, hipStream_t s) {
+  const listtree_shape& sh = tree->sh;
+  const uint64_t c0 = listtree_chunk_of(sh, tree->count), c1 = listtree_chunks(sh, tree->count + n);
+  if (!sh.packed) {
+    Bump b(ws, bls381_list_tree_append_workspace_size(tree, n));
+    int32_t* err = b.take<int32_t>(1);
+    HIPC(hipMemsetAsync(err, 0, 4, s));
+    LAUNCH("listtree_leaves", s, dim3(grid_for(n)), dim3(KBLOCK), k_ssz_root, n, (const uint8_t*)listtree_item(tree, tree->count),
+           (size_t)sh.item_size, (const uint32_t*)tree->prog, tree->plen, tree->store + sh.off[0] + 32 * tree->count, err);
+  }
+  const listtree_levels lv{sh, c1};
+  for (const merkle_pass& ps : listtree_range_plan(sh, c0, c1))
+    LAUNCH("listtree_reduce", s, dim3((unsigned)ps.tiles), dim3(MERKLE_TILE / 2), k_listtree_reduce, tree->store, lv,
+           (const uint8_t*)c->ztab, ps.h0, ps.steps, ps.tile0, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+  tree->count += n;
+  return 0;
+}
+
+int bls381_list_tree_append_device(bls381_list_tree* tree, size_t n, const uint8_t* d_items, void* d_workspace,
+                                   void* stream) {
+  return guarded([&]() -> int {
+    if (!tree || !listtree_fits(tree, n) || (n && !d_items) ||
+        (bls381_list_tree_append_workspace_size(tree, n) && !d_workspace))
+      return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(hipMemcpyAsync(listtree_item(tree, tree->count), d_items, n * tree->sh.item_size, hipMemcpyDeviceToDevice, s));
+    return listtree_append_impl(c, tree, n, d_workspace, s);
+  });
+}
+
+int bls381_list_tree_append(bls381_list_tree* tree, size_t n, const uint8_t* items) {
+  return guarded([&]() -> int {
+    if (!tree || !listtree_fits(tree, n) || (n && !items)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t* d_ws = nullptr;
+    TRY(hc.carve([&](Bump& b) { d_ws = b.take<uint8_t>(bls381_list_tree_append_workspace_size(tree, n)); }));
+    TRY(hc.upload(listtree_item(tree, tree->count), items, n * tree->sh.item_size));
+    TRY(listtree_append_impl(c, tree, n, d_ws, hc.s));
+    return hc.finish();
+  });
+}
+
+// the workspace of an update: flag rows, tile lists and their lengths (listtree_update_layout)
+size_t bls381_list_tree_update_workspace_size(const bls381_list_tree* tree, size_t n_upd) {
+  if (!tree || n_upd == 0 || n_upd > (size_t)INT32_MAX) return 0;
+  if (tree->sh.packed && listtree_passes(tree->sh) == 0) return 0;
+  return align256(4 * (size_t)listtree_update_layout(tree->sh, n_upd).words);
+}
+
+// launches of an update, whatever n_upd is: the scatter, [composite: the leaves], and, in a tree
+// with P = listtree_passes() > 0 passes, the mark, the compaction and the P passes
+int bls381_list_tree_update_device(bls381_list_tree* tree, size_t n_upd, const uint32_t* d_indices, size_t off,
+                                   size_t len, const uint8_t* d_values, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!tree || n_upd > (size_t)INT32_MAX || off > tree->sh.item_size || len > tree->sh.item_size - off)
+      return BLS381_EARG;
+    if (n_upd == 0 || len == 0) return 0;
+    if (!d_indices || !d_values || ((uintptr_t)d_indices & 3) ||
+        (bls381_list_tree_update_workspace_size(tree, n_upd) && !d_workspace))
+      return BLS381_EARG;
+    if (tree->count == 0) return 0;   // every index is at or above the count
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const listtree_shape& sh = tree->sh;
+    const uint64_t chunks = listtree_chunks_now(tree);
+    const listtree_update_ws w = listtree_update_layout(sh, n_upd);
+    uint32_t* ws = (uint32_t*)d_workspace;
+    LAUNCH("listtree_scatter", s, dim3(grid_for(n_upd * len)), dim3(KBLOCK), k_listtree_scatter, n_upd, d_indices,
+           d_values, (uint32_t)off, (uint32_t)len, tree->store, sh, tree->count);
+    if (!sh.packed) {
+      int32_t* err = (int32_t*)(ws + w.err);
+      HIPC(hipMemsetAsync(err, 0, 4, s));
+      LAUNCH("listtree_leaves_idx", s, dim3(grid_for(n_upd)), dim3(KBLOCK), k_listtree_leaves, n_upd, d_indices,
+             tree->store, sh, tree->count, (const uint32_t*)tree->prog, tree->plen, err);
+    }
+    if (w.passes == 0) return 0;
+    const listtree_marks m = listtree_make_marks(w, chunks);
+    HIPC(hipMemsetAsync(ws, 0, 4 * (size_t)w.flag_words, s));
+    LAUNCH("listtree_mark", s, dim3(grid_for(n_upd)), dim3(KBLOCK), k_listtree_mark, n_upd, d_indices, sh, tree->count,
+           m, ws);
+    LAUNCH("listtree_compact", s, dim3(w.passes), dim3(LISTTREE_COMPACT_LANES), k_listtree_compact, m, ws);
+    const listtree_levels lv{sh, chunks};
+    for (uint32_t k = 0; k < w.passes; ++k) {
+      const uint32_t h0 = k * MERKLE_TILE_LOG;
+      LAUNCH("listtree_reduce", s, dim3((unsigned)std::min<uint64_t>(n_upd, m.tiles[k])), dim3(MERKLE_TILE / 2),
+             k_listtree_reduce, tree->store, lv, (const uint8_t*)c->ztab, h0, std::min(MERKLE_TILE_LOG, sh.top - h0),
+             (uint64_t)0, (const uint32_t*)(ws + m.list[k]), (const uint32_t*)(ws + m.lens + k));
+    }
+    return 0;
+  });
+}
+
+int bls381_list_tree_update(bls381_list_tree* tree, size_t n_upd, const uint32_t* indices, size_t off, size_t len,
+                            const uint8_t* values) {
+  return guarded([&]() -> int {
+    if (!tree || n_upd > (size_t)INT32_MAX || off > tree->sh.item_size || len > tree->sh.item_size - off)
+      return BLS381_EARG;
+    if (n_upd == 0 || len == 0) return 0;
+    if (!indices || !values) return BLS381_EARG;
+    for (size_t t = 0; t < n_upd; ++t)
+      if (indices[t] >= tree->count) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    // repeated indices are applied in order: the last one wins, the earlier ones are dropped here
+    std::vector<uint32_t> idx;
+    std::vector<uint8_t> vals;
+    {
+      std::unordered_set<uint32_t> seen;
+      std::vector<size_t> keep;
+      for (size_t t = n_upd; t-- > 0;)
+        if (seen.insert(indices[t]).second) keep.push_back(t);
+      idx.reserve(keep.size());
+      vals.reserve(keep.size() * len);
+      for (size_t q = keep.size(); q-- > 0;) {
+        idx.push_back(indices[keep[q]]);
+        vals.insert(vals.end(), values + keep[q] * len, values + (keep[q] + 1) * len);
+      }
+    }
+    const size_t m = idx.size();
+    HostCall hc(c);
+    uint32_t* d_idx;
+    uint8_t *d_vals, *d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      d_idx = b.take<uint32_t>(m);
+      d_vals = b.take<uint8_t>(m * len);
+      d_ws = b.take<uint8_t>(bls381_list_tree_update_workspace_size(tree, m));
+    }));
+    TRY(hc.upload(d_idx, idx.data(), 4 * m));
+    TRY(hc.upload(d_vals, vals.data(), m * len));
+    TRY(bls381_list_tree_update_device(tree, m, d_idx, off, len, d_vals, d_ws, hc.s));
+    return hc.finish();   // idx and vals outlive the copies: finish() synchronises
+  });
+}
+
+// node (d, 0) -- the item bytes of a packed list with one chunk, Z[0] of an empty list -- with
+// the optional mix_in_length(count): k_merkle_finish with nothing left to fold
+static int listtree_root_impl(Ctx* c, const bls381_list_tree* tree, int mix, uint8_t* d_root, hipStream_t s) {
+  const uint32_t d = bls381_list_tree_depth(tree);
+  const uint8_t* node = tree->count ? tree->store + tree->sh.off[d] : nullptr;
+  LAUNCH("listtree_root", s, dim3(1), dim3(64), k_merkle_finish, node, (uint8_t*)nullptr, (const merkle_level*)nullptr,
+         (const uint8_t*)c->ztab, d, d, (uint64_t)0, mix, tree->count, d_root);
+  return 0;
+}
+
+int bls381_list_tree_root_device(bls381_list_tree* tree, int mix_length, uint8_t* d_root32, void* stream) {
+  return guarded([&]() -> int {
+    if (!tree || !d_root32 || !aligned4(d_root32)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    return listtree_root_impl(c, tree, mix_length, d_root32, (hipStream_t)stream);
+  });
+}
+
+int bls381_list_tree_root(bls381_list_tree* tree, int mix_length, uint8_t root[32]) {
+  return guarded([&]() -> int {
+    if (!tree || !root) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    uint8_t* d_root;
+    TRY(hc.carve([&](Bump& b) { d_root = b.take<uint8_t>(32); }));
+    TRY(listtree_root_impl(c, tree, mix_length, d_root, hc.s));
+    TRY(hc.download(root, d_root, 32));
+    return hc.finish();
+  });
+}
+
+static bool listtree_proofs_args_ok(const bls381_list_tree* tree, size_t n_idx, const void* indices, const void* proofs,
+                                    size_t proof_stride, const void* root) {
+  if (!tree || n_idx > (size_t)INT32_MAX || proof_stride < (size_t)32 * bls381_list_tree_depth(tree)) return false;
+  return root && (n_idx == 0 || (indices && (proofs || bls381_list_tree_depth(tree) == 0)));
+}
+
+int bls381_list_tree_proofs_device(bls381_list_tree* tree, size_t n_idx, const uint64_t* d_chunk_indices,
+                                   uint8_t* d_proofs, size_t proof_stride, uint8_t* d_root32, void* stream) {
+  return guarded([&]() -> int {
+    if (!listtree_proofs_args_ok(tree, n_idx, d_chunk_indices, d_proofs, proof_stride, d_root32) ||
+        !aligned4(d_proofs) || !aligned4(d_root32) || (proof_stride & 3) || ((uintptr_t)d_chunk_indices & 7))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t d = bls381_list_tree_depth(tree);
+    TRY(listtree_root_impl(c, tree, 0, d_root32, s));
+    LAUNCH("listtree_proofs", s, dim3(grid_for(n_idx * d)), dim3(KBLOCK), k_listtree_proofs, n_idx, d_chunk_indices, d,
+           listtree_chunks_now(tree), (const uint8_t*)tree->store, tree->sh, (const uint8_t*)c->ztab, d_proofs,
+           proof_stride);
+    return 0;
+  });
+}
+
+int bls381_list_tree_proofs(bls381_list_tree* tree, size_t n_idx, const uint64_t* chunk_indices, uint8_t* proofs,
+                            size_t proof_stride, uint8_t root[32]) {
+  return guarded([&]() -> int {
+    if (!listtree_proofs_args_ok(tree, n_idx, chunk_indices, proofs, proof_stride, root)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = listtree_ctx(tree, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t row = (size_t)32 * bls381_list_tree_depth(tree);
+    uint8_t *d_proofs, *d_root;
+    uint64_t* d_idx;
+    TRY(hc.carve([&](Bump& b) {
+      d_idx = b.take<uint64_t>(n_idx);
+      d_proofs = b.take<uint8_t>(row * n_idx);
+      d_root = b.take<uint8_t>(32);
+    }));
+    TRY(hc.upload(d_idx, chunk_indices, 8 * n_idx));
+    TRY(bls381_list_tree_proofs_device(tree, n_idx, d_idx, d_proofs, row, d_root, hc.s));
+    // packed on the device; the caller's rows are proof_stride apart and only their proofs are written
+    if (row && n_idx)
+      HIPC(hipMemcpy2DAsync(proofs, proof_stride, d_proofs, row, row, n_idx, hipMemcpyDeviceToHost, hc.s));
+    TRY(hc.download(root, d_root, 32));
     return hc.finish();
   });
 }

@@ -14,6 +14,7 @@
 #include "bls381_ssz.hpp"
 #include "bls381_merkle.hpp"
 #include "bls381_deptree.hpp"
+#include "bls381_listtree.hpp"
 #include "bls381_shuffle.hpp"
 #include "bls381_epoch.hpp"
 #include "bls381_keytable.hpp"
@@ -1543,14 +1544,15 @@ struct merkle_table_levels {
   __device__ __forceinline__ merkle_level in(uint32_t h) const { return {L[h].base, L[h].count, L[h].off}; }
   __device__ __forceinline__ merkle_level out(uint32_t h) const { return in(h); }
 };
+// (merkle_reduce_at: the workgroup's tile number t given by the caller -- a list tree's passes
+// take it from a list, bls381_listtree.hpp)
 template <class Lv>
-__device__ __forceinline__ void merkle_reduce_tile(const uint8_t* __restrict__ in, uint8_t* nodes, const Lv& lv,
-                                                   const uint8_t* __restrict__ ztab, uint32_t h0, uint32_t steps,
-                                                   uint64_t tile0) {
+__device__ __forceinline__ void merkle_reduce_at(const uint8_t* __restrict__ in, uint8_t* nodes, const Lv& lv,
+                                                 const uint8_t* __restrict__ ztab, uint32_t h0, uint32_t steps,
+                                                 const uint64_t t) {
   constexpr uint32_t T = MERKLE_TILE / 2;
   __shared__ uint32_t tile[2][8][MERKLE_LDS_ROW];
   const uint32_t l = threadIdx.x;
-  const uint64_t t = tile0 + blockIdx.x;
   g_u32* out = (g_u32*)nodes;
   uint64_t j = t * T + l;
   uint32_t v[8];
@@ -1580,6 +1582,12 @@ __device__ __forceinline__ void merkle_reduce_tile(const uint8_t* __restrict__ i
     j = ((t * T) >> s) + l;
     p ^= 1;
   }
+}
+template <class Lv>
+__device__ __forceinline__ void merkle_reduce_tile(const uint8_t* __restrict__ in, uint8_t* nodes, const Lv& lv,
+                                                   const uint8_t* __restrict__ ztab, uint32_t h0, uint32_t steps,
+                                                   uint64_t tile0) {
+  merkle_reduce_at(in, nodes, lv, ztab, h0, steps, tile0 + blockIdx.x);
 }
 __global__ void __launch_bounds__(MERKLE_TILE / 2) k_merkle_reduce(const uint8_t* __restrict__ in, uint8_t* nodes,
                                                                   const merkle_level* __restrict__ lv,
@@ -1707,6 +1715,91 @@ __global__ void __launch_bounds__(KBLOCK) k_deptree_gather(size_t n_idx, const u
   const uint32_t h = (uint32_t)(t % sh.depth);
   const uint64_t i = indices ? indices[q] : index_base + q;
   g_cu32* src = deptree_sibling_src(sh, (g_cu32*)store, k, i, h, (g_cu32*)ptab, (g_cu32*)ztab);
+  g_u32* dst = (g_u32*)(proofs + q * proof_stride + 32 * h);
+  for (int w = 0; w < 8; ++w) dst[w] = src[w];
+}
+
+// ------------------------------------------------- SSZ list trees kept in memory --
+// (storage, the dirty-tile rule and the update's workspace: bls381_listtree.hpp)
+// bytes [off, off + len) of item indices[t] from values + t len, one lane per byte
+__global__ void __launch_bounds__(KBLOCK) k_listtree_scatter(size_t n_upd, const uint32_t* __restrict__ indices,
+                                                             const uint8_t* __restrict__ values, uint32_t off,
+                                                             uint32_t len, uint8_t* store, listtree_shape sh,
+                                                             uint64_t count) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_upd * len) return;
+  listtree_scatter_byte(sh, count, indices, values, off, len, g / len, (uint32_t)(g % len), store);
+}
+
+// the flags of the tiles that hold an updated chunk, one lane per update (ws: the update's workspace as words)
+__global__ void __launch_bounds__(KBLOCK) k_listtree_mark(size_t n_upd, const uint32_t* __restrict__ indices,
+                                                          listtree_shape sh, uint64_t count, listtree_marks m,
+                                                          uint32_t* ws) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_upd) return;
+  listtree_mark(sh, count, m, indices, t, ws);
+}
+
+// the k_ssz_root of an update: the root of item indices[t] of the store to node indices[t] of row
+// 0, read after the scatter -- repeated indices write equal bytes
+__global__ void __launch_bounds__(KBLOCK) k_listtree_leaves(size_t n_upd, const uint32_t* __restrict__ indices,
+                                                            uint8_t* store, listtree_shape sh, uint64_t count,
+                                                            const uint32_t* __restrict__ prog, uint32_t plen,
+                                                            int32_t* __restrict__ err) {
+  const size_t t = item_index<1>();
+  if (t >= n_upd) return;
+  const uint64_t i = indices[t];
+  if (i >= count) return;
+  uint32_t stk[SSZ_STACK][8];
+  uint32_t r[8];
+  if (!ssz_run(r, store + i * sh.item_size, prog, plen, stk)) { *err = 1; return; }
+  merkle_store((g_u32*)(store + sh.off[0] + 32 * i), r);
+}
+
+// Workgroup k: pass k's flag row into its tile list, ascending, and the list's length.
+__global__ void __launch_bounds__(LISTTREE_COMPACT_LANES) k_listtree_compact(listtree_marks m, uint32_t* ws) {
+  __shared__ uint32_t cnt[LISTTREE_COMPACT_LANES];
+  const uint32_t k = blockIdx.x, l = threadIdx.x;
+  const uint32_t* flags = ws + m.flags[k];
+  uint32_t lo, hi;
+  listtree_segment(m.tiles[k], l, &lo, &hi);
+  cnt[l] = listtree_segment_count(flags, lo, hi);
+  __syncthreads();
+  uint32_t before = 0;
+  for (uint32_t q = 0; q < l; ++q) before += cnt[q];
+  listtree_segment_write(flags, lo, hi, ws + m.list[k] + before);
+  if (l == LISTTREE_COMPACT_LANES - 1) ws[m.lens + k] = before + cnt[l];
+}
+
+// One pass of a re-hash: the tile reduction over the stored row of level h0, written back to
+// the stored rows.  With a list, workgroup b takes tile list[b] and returns at once when b is at
+// or above *list_len -- the whole workgroup, before the reduction's first barrier; without one,
+// tile tile0 + b (an append).
+__global__ void __launch_bounds__(MERKLE_TILE / 2) k_listtree_reduce(uint8_t* store, listtree_levels lv,
+                                                                    const uint8_t* __restrict__ ztab, uint32_t h0,
+                                                                    uint32_t steps, uint64_t tile0,
+                                                                    const uint32_t* __restrict__ list,
+                                                                    const uint32_t* __restrict__ list_len) {
+  uint64_t t = tile0 + blockIdx.x;
+  if (list) {
+    if (blockIdx.x >= *list_len) return;
+    t = list[blockIdx.x];
+  }
+  merkle_reduce_at(store + lv.sh.off[h0], store, lv, ztab, h0, steps, t);
+}
+
+// The proofs at the current count of n_idx chunk indices, one lane per sibling: a stored node or
+// Z[h], to proofs + t proof_stride + 32 h (4-byte aligned), as k_merkle_proofs.
+__global__ void __launch_bounds__(KBLOCK) k_listtree_proofs(size_t n_idx, const uint64_t* __restrict__ indices,
+                                                            uint32_t depth, uint64_t chunks,
+                                                            const uint8_t* __restrict__ store, listtree_shape sh,
+                                                            const uint8_t* __restrict__ ztab,
+                                                            uint8_t* __restrict__ proofs, size_t proof_stride) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_idx * depth) return;
+  const size_t q = t / depth;
+  const uint32_t h = (uint32_t)(t % depth);
+  g_cu32* src = listtree_sibling_src(sh, (g_cu32*)store, chunks, indices[q], h, (g_cu32*)ztab);
   g_u32* dst = (g_u32*)(proofs + q * proof_stride + 32 * h);
   for (int w = 0; w < 8; ++w) dst[w] = src[w];
 }

@@ -25,6 +25,7 @@
 #include "bls381_ssz.hpp"
 #include "bls381_merkle.hpp"
 #include "bls381_deptree.hpp"
+#include "bls381_listtree.hpp"
 #include "bls381_keytable.hpp"
 
 // ---- stand-ins for the HIP types and runtime calls that bls381_scope.hpp is written against.
@@ -822,6 +823,227 @@ int hc_deptree_plan(uint64_t capacity, uint64_t count, uint64_t n, uint64_t* out
     out[2 + 4 * k] = passes[k].steps;
     out[3 + 4 * k] = passes[k].tile0;
     out[4 + 4 * k] = passes[k].tiles;
+  }
+  return 0;
+}
+
+// ---- SSZ list trees kept in memory (bls381_listtree.hpp): what k_listtree_scatter / _mark /
+// _leaves / _compact / _reduce / _proofs run, workgroups and lanes as plain loops -- the flag
+// rows, the compaction and the tile lists included.  The store and the update's workspace have
+// their exact sizes, so the sanitized build sees any access outside them.
+namespace {
+struct HcListTree {
+  listtree_shape sh{};
+  uint64_t count = 0;
+  std::vector<uint32_t> store, ztab, prog;
+  uint8_t* bytes() { return (uint8_t*)store.data(); }
+  uint64_t chunks() const { return listtree_chunks(sh, count); }
+  uint32_t depth() const { return merkle_chunk_depth(chunks()); }
+};
+
+// k_listtree_reduce over a pass's workgroups: tile list[b] for b below the list's length (a
+// workgroup at or above it returns), or tile0 + b without a list
+void hc_listtree_pass(HcListTree* t, const listtree_levels& lv, const merkle_pass& ps, const uint32_t* list,
+                      const uint32_t* list_len, int threads) {
+  if (threads < 1) threads = 1;
+  std::vector<std::thread> pool;
+  for (int k = 0; k < threads; ++k)
+    pool.emplace_back([&, k] {
+      for (uint64_t b = (uint64_t)k; b < ps.tiles; b += (uint64_t)threads) {
+        if (list && b >= *list_len) continue;
+        hc_merkle_tile_run(t->store.data() + t->sh.off[ps.h0] / 4, t->store.data(), lv, t->ztab.data(), ps,
+                           list ? list[b] : ps.tile0 + b);
+      }
+    });
+  for (auto& th : pool) th.join();
+}
+
+// k_listtree_mark and k_listtree_compact of an update: the workspace's flag rows, tile lists and lengths
+void hc_listtree_dirty(const HcListTree* t, size_t n_upd, const uint32_t* indices, const listtree_marks& m,
+                       std::vector<uint32_t>& ws) {
+  for (size_t u = 0; u < n_upd; ++u) listtree_mark(t->sh, t->count, m, indices, u, ws.data());
+  for (uint32_t k = 0; k < m.passes; ++k) {
+    uint32_t cnt[LISTTREE_COMPACT_LANES], lo, hi;
+    const uint32_t* flags = ws.data() + m.flags[k];
+    for (uint32_t l = 0; l < LISTTREE_COMPACT_LANES; ++l) {
+      listtree_segment(m.tiles[k], l, &lo, &hi);
+      cnt[l] = listtree_segment_count(flags, lo, hi);
+    }
+    uint32_t before = 0;
+    for (uint32_t l = 0; l < LISTTREE_COMPACT_LANES; ++l) {
+      listtree_segment(m.tiles[k], l, &lo, &hi);
+      listtree_segment_write(flags, lo, hi, ws.data() + m.list[k] + before);
+      before += cnt[l];
+    }
+    ws[m.lens + k] = before;
+  }
+}
+}  // namespace
+
+// bls381_list_tree_create: the tree, or null for arguments the engine rejects
+void* hc_listtree_create(uint64_t capacity, uint64_t item_size, const uint32_t* prog, uint32_t plen) {
+  const bool packed = !prog && plen == 0;
+  if (!listtree_args_ok(capacity, item_size, packed) || (!packed && !ssz_prog_ok(prog, plen, item_size))) return nullptr;
+  auto* t = new HcListTree();
+  uint64_t bytes = 0;
+  t->sh = listtree_make_shape(capacity, (uint32_t)item_size, packed, &bytes);
+  t->store.assign(bytes / 4, 0);
+  if (!packed) t->prog.assign(prog, prog + plen);
+  uint8_t z[MERKLE_ZERO_TABLE_BYTES];
+  merkle_zero_table(z);
+  t->ztab.assign(MERKLE_ZERO_TABLE_BYTES / 4, 0);
+  std::memcpy(t->ztab.data(), z, sizeof(z));
+  return t;
+}
+void hc_listtree_destroy(void* tree) { delete (HcListTree*)tree; }
+uint64_t hc_listtree_count(const void* tree) { return tree ? ((const HcListTree*)tree)->count : 0; }
+uint32_t hc_listtree_depth(const void* tree) { return tree ? ((const HcListTree*)tree)->depth() : 0; }
+
+// bls381_list_tree_append: 0, or -2 for arguments the engine rejects
+int hc_listtree_append(void* tree, size_t n, const uint8_t* items, int threads) {
+  HcListTree* t = (HcListTree*)tree;
+  if (!t || n > t->sh.capacity - t->count || (n && !items)) return -2;
+  if (n == 0) return 0;
+  const listtree_shape& sh = t->sh;
+  std::memcpy(t->bytes() + t->count * sh.item_size, items, n * sh.item_size);
+  const uint64_t c0 = listtree_chunk_of(sh, t->count), c1 = listtree_chunks(sh, t->count + n);
+  if (!sh.packed) {
+    static thread_local uint32_t stk[SSZ_STACK][8];
+    for (uint64_t i = t->count; i < t->count + n; ++i) {
+      uint32_t r[8];
+      if (!ssz_run(r, t->bytes() + i * sh.item_size, t->prog.data(), (uint32_t)t->prog.size(), stk)) return -1;
+      merkle_store(t->store.data() + sh.off[0] / 4 + 8 * i, r);
+    }
+  }
+  const listtree_levels lv{sh, c1};
+  for (const merkle_pass& ps : listtree_range_plan(sh, c0, c1)) hc_listtree_pass(t, lv, ps, nullptr, nullptr, threads);
+  t->count += n;
+  return 0;
+}
+
+// bls381_list_tree_update (device_form = 0: an index at or above the count is rejected, repeated
+// indices dropped but for the last) or bls381_list_tree_update_device (1: such an index is
+// skipped, repeated ones all run): 0, or -2 for arguments the engine rejects
+int hc_listtree_update(void* tree, size_t n_upd, const uint32_t* indices, size_t off, size_t len, const uint8_t* values,
+                       int device_form, int threads) {
+  HcListTree* t = (HcListTree*)tree;
+  if (!t || n_upd > (size_t)INT32_MAX || off > t->sh.item_size || len > t->sh.item_size - off) return -2;
+  if (n_upd == 0 || len == 0) return 0;
+  if (!indices || !values) return -2;
+  std::vector<uint32_t> idx(indices, indices + n_upd);
+  std::vector<uint8_t> vals(values, values + n_upd * len);
+  if (!device_form) {
+    for (size_t u = 0; u < n_upd; ++u)
+      if (indices[u] >= t->count) return -2;
+    std::map<uint32_t, size_t> last;
+    for (size_t u = 0; u < n_upd; ++u) last[indices[u]] = u;
+    idx.clear();
+    vals.clear();
+    for (size_t u = 0; u < n_upd; ++u)
+      if (last[indices[u]] == u) {
+        idx.push_back(indices[u]);
+        vals.insert(vals.end(), values + u * len, values + (u + 1) * len);
+      }
+    n_upd = idx.size();
+  }
+  if (t->count == 0) return 0;
+  const listtree_shape& sh = t->sh;
+  for (size_t g = 0; g < n_upd * len; ++g)
+    listtree_scatter_byte(sh, t->count, idx.data(), vals.data(), (uint32_t)off, (uint32_t)len, g / len, (uint32_t)(g % len),
+                          t->bytes());
+  if (!sh.packed) {
+    static thread_local uint32_t stk[SSZ_STACK][8];
+    for (size_t u = 0; u < n_upd; ++u) {
+      const uint64_t i = idx[u];
+      if (i >= t->count) continue;
+      uint32_t r[8];
+      if (!ssz_run(r, t->bytes() + i * sh.item_size, t->prog.data(), (uint32_t)t->prog.size(), stk)) return -1;
+      merkle_store(t->store.data() + sh.off[0] / 4 + 8 * i, r);
+    }
+  }
+  const listtree_update_ws w = listtree_update_layout(sh, n_upd);
+  if (w.passes == 0) return 0;
+  const listtree_marks m = listtree_make_marks(w, t->chunks());
+  std::vector<uint32_t> ws(w.words, 0xEEEEEEEEu);
+  std::fill(ws.begin(), ws.begin() + w.flag_words, 0);
+  hc_listtree_dirty(t, n_upd, idx.data(), m, ws);
+  const listtree_levels lv{sh, t->chunks()};
+  for (uint32_t k = 0; k < w.passes; ++k) {
+    const uint32_t h0 = k * MERKLE_TILE_LOG;
+    const merkle_pass ps{h0, std::min(MERKLE_TILE_LOG, sh.top - h0), 0, std::min<uint64_t>(n_upd, m.tiles[k])};
+    hc_listtree_pass(t, lv, ps, ws.data() + m.list[k], ws.data() + m.lens + k, threads);
+  }
+  return 0;
+}
+
+// bls381_list_tree_root (k_merkle_finish with nothing left to fold): 0 or -2
+int hc_listtree_root(void* tree, int mix_length, uint8_t* root32) {
+  HcListTree* t = (HcListTree*)tree;
+  if (!t || !root32) return -2;
+  uint32_t v[8];
+  merkle_load(v, t->count ? (const uint32_t*)t->store.data() + t->sh.off[t->depth()] / 4 : (const uint32_t*)t->ztab.data());
+  if (mix_length) merkle_mix_in_length(v, t->count);
+  uint32_t out[8];
+  merkle_store(out, v);
+  std::memcpy(root32, out, 32);
+  return 0;
+}
+
+// bls381_list_tree_proofs (the root, then k_listtree_proofs one (index, level) per iteration): 0 or -2
+int hc_listtree_proofs(void* tree, size_t n_idx, const uint64_t* chunk_indices, uint8_t* proofs, size_t proof_stride,
+                       uint8_t* root32) {
+  HcListTree* t = (HcListTree*)tree;
+  if (!t) return -2;
+  const uint32_t d = t->depth();
+  if (n_idx > (size_t)INT32_MAX || proof_stride < (size_t)32 * d || !root32 || (n_idx && (!chunk_indices || (!proofs && d))))
+    return -2;
+  hc_listtree_root(tree, 0, root32);
+  for (size_t q = 0; q < n_idx; ++q)
+    for (uint32_t h = 0; h < d; ++h)
+      std::memcpy(proofs + q * proof_stride + 32 * (size_t)h,
+                  listtree_sibling_src(t->sh, (const uint32_t*)t->store.data(), t->chunks(), chunk_indices[q], h,
+                                       (const uint32_t*)t->ztab.data()),
+                  32);
+  return 0;
+}
+
+// bls381_list_tree_read: 0 or -2
+int hc_listtree_read(void* tree, size_t first, size_t n, uint8_t* items_out) {
+  HcListTree* t = (HcListTree*)tree;
+  if (!t || first > t->count || n > t->count - first || (n && !items_out)) return -2;
+  std::memcpy(items_out, t->bytes() + first * t->sh.item_size, n * t->sh.item_size);
+  return 0;
+}
+// the item bytes of the whole capacity, behind the count included (they must read as zero there)
+int hc_listtree_read_capacity(void* tree, uint8_t* items_out) {
+  HcListTree* t = (HcListTree*)tree;
+  if (!t || !items_out) return -2;
+  std::memcpy(items_out, t->bytes(), t->sh.capacity * t->sh.item_size);
+  return 0;
+}
+
+// The plan of an update of the given indices at the tree's current count, the tree unchanged:
+// out = {launches, passes, then per pass {h0, steps, workgroups launched, list length, the
+// list's tiles ...}}, at most out_cap words.  0, or -2 for a rejected call or a short `out`.
+int hc_listtree_plan(void* tree, size_t n_upd, const uint32_t* indices, uint64_t* out, size_t out_cap) {
+  HcListTree* t = (HcListTree*)tree;
+  if (!t || n_upd == 0 || n_upd > (size_t)INT32_MAX || !indices || !out || out_cap < 2) return -2;
+  const listtree_update_ws w = listtree_update_layout(t->sh, n_upd);
+  const listtree_marks m = listtree_make_marks(w, t->chunks());
+  std::vector<uint32_t> ws(w.words, 0xEEEEEEEEu);
+  std::fill(ws.begin(), ws.begin() + w.flag_words, 0);
+  if (w.passes) hc_listtree_dirty(t, n_upd, indices, m, ws);
+  size_t at = 0;
+  out[at++] = listtree_update_launches(t->sh);
+  out[at++] = w.passes;
+  for (uint32_t k = 0; k < w.passes; ++k) {
+    const uint32_t h0 = k * MERKLE_TILE_LOG, len = ws[m.lens + k];
+    if (at + 4 + len > out_cap) return -2;
+    out[at++] = h0;
+    out[at++] = std::min(MERKLE_TILE_LOG, t->sh.top - h0);
+    out[at++] = std::min<uint64_t>(n_upd, m.tiles[k]);
+    out[at++] = len;
+    for (uint32_t q = 0; q < len; ++q) out[at++] = ws[m.list[k] + q];
   }
   return 0;
 }

@@ -539,6 +539,85 @@ int bls381_deposit_tree_deposits_device(bls381_deposit_tree* tree, uint64_t k, u
                                         const uint8_t* d_deposit_data, uint8_t* d_deposits, void* d_workspace,
                                         void* stream);
 
+/* ---- SSZ list trees kept on the device: update items, re-root by dirty paths ---- */
+/* A list of count <= capacity items of item_size bytes, packed, that lives in device memory with
+ * the Merkle tree over its chunks, takes in-place updates as well as appends, and re-hashes only
+ * the tiles on the paths of what changed: state.validator_registry,
+ * state.balances and the root vectors held across slots.  The mode is fixed at creation.
+ *   composite (prog != NULL): chunk i is the root program over item i, as in bls381_ssz_root_batch,
+ *            with its checks (a well-formed program of at most 512 words and 64 chunks that reads
+ *            inside the item).  List[Validator], any list or vector of fixed-size containers.
+ *   packed   (prog == NULL, prog_len == 0): item_size is 1, 2, 4, 8, 16 or 32 and chunk j is bytes
+ *            [32 j, 32 j + 32) of the packed items, zero behind the last item.  List[uint64],
+ *            Vector[Bytes32, N].
+ * With `chunks` the number of chunks at the current count and d = ceil(log2 chunks) (0 for
+ * chunks <= 1):
+ *   root     node (d, 0) of the tree over the chunks with zero chunks behind them, and with
+ *            mix_length != 0 mix_in_length(root, count): after every sequence of operations what
+ *            bls381_ssz_list_root (composite) or bls381_merkle_root(n = chunks, first = 0, depth =
+ *            d, mix_length, length = count) (packed) gives over the items as they stand.  count ==
+ *            0 gives the zero chunk, mixed with 0 when asked.  d moves as the list grows.
+ *   append   items count .. count+n-1.  count + n > capacity is BLS381_EARG and nothing changes;
+ *            n == 0 is BLS381_OK and runs nothing.
+ *   update   bytes [off, off+len) of item indices[t] become values[t len .. (t+1) len): off = 0,
+ *            len = item_size replaces items; off = 113, len = 8 on Validator records sets
+ *            effective_balance.  off + len > item_size is BLS381_EARG; len == 0 or n_upd == 0 is
+ *            BLS381_OK and runs nothing.  Host-pointer form: an index at or above the count is
+ *            BLS381_EARG and nothing changes; repeated indices are applied in order (the last
+ *            wins).  Device form: the host does not see the indices; an index at or above the
+ *            count is skipped; repeated indices with byte-equal values are fine, with different
+ *            values each byte ends up holding one of the given values.  In every case the tree is
+ *            afterwards the tree of what the store holds: leaves are re-hashed from the store.
+ *   proofs   siblings 0 .. d-1 of each chunk index at the current count and the unmixed root,
+ *            with the proof rows of bls381_merkle_proofs: proof_stride >= 32 d, bytes of a row
+ *            past the proof left alone; a chunk index at or above `chunks` (and below 2^d) gets
+ *            the proof of a zero chunk; with d == 0 nothing is written.  They verify under
+ *            bls381_merkle_branch_batch(depth = d).  There are no queries at earlier counts
+ *            (in-place updates rule them out: that is the deposit tree's job).
+ *   read     copies items [first, first+n) to the host; first + n above the count is BLS381_EARG.
+ *   items_device  the device address of item 0 (item i at + i item_size), valid until destroy and
+ *            read-only for the caller: what bls381_active_indices_device,
+ *            bls381_proposer_indices_device and bls381_ssz_list_root_device take.
+ * One thread and one stream at a time use a tree, or the caller orders them.  Host-pointer forms
+ * run on the engine's own stream and return synchronised; device forms are queued on `stream`,
+ * never synchronise and read nothing back to the host.  The count is kept on the host and moves
+ * when an append is queued.  An update or append queues a number of launches that depends on the
+ * capacity alone, never on n or n_upd.  The tree belongs to the device current at creation (calls
+ * with another device current return BLS381_EARG) and holds item_size + 64 bytes per item of
+ * capacity (composite) or 2 item_size (packed).  Workspaces hold *_workspace_size bytes (0 for
+ * arguments the call rejects, and where the call needs none) and belong to the call.
+ * BLS381_EARG: capacity 0 or above 2^31 - 1; item_size 0; a packed item_size outside the six; a
+ * program bls381_ssz_root_batch would reject; a NULL argument that is needed (the tree always;
+ * data and outputs when the item count is not 0; the workspace of a device form whose size
+ * function is not 0); n_upd or n_idx above 2^31 - 1; in the device forms d_proofs, proof_stride
+ * and d_root32 not 4-byte, d_indices not 4-byte or d_chunk_indices not 8-byte aligned.  The
+ * program is copied at creation.  destroy(NULL) is a no-op; count, capacity and depth of NULL
+ * are 0. */
+typedef struct bls381_list_tree bls381_list_tree;
+int bls381_list_tree_create(size_t capacity, size_t item_size, const uint32_t* prog, uint32_t prog_len,
+                            bls381_list_tree** out);
+void bls381_list_tree_destroy(bls381_list_tree* tree);
+size_t bls381_list_tree_count(const bls381_list_tree* tree);
+size_t bls381_list_tree_capacity(const bls381_list_tree* tree);
+uint32_t bls381_list_tree_depth(const bls381_list_tree* tree);   /* d at the current count */
+const uint8_t* bls381_list_tree_items_device(const bls381_list_tree* tree);
+int bls381_list_tree_read(bls381_list_tree* tree, size_t first, size_t n, uint8_t* items_out);
+size_t bls381_list_tree_append_workspace_size(const bls381_list_tree* tree, size_t n);
+int bls381_list_tree_append(bls381_list_tree* tree, size_t n, const uint8_t* items);
+int bls381_list_tree_append_device(bls381_list_tree* tree, size_t n, const uint8_t* d_items, void* d_workspace,
+                                   void* stream);
+size_t bls381_list_tree_update_workspace_size(const bls381_list_tree* tree, size_t n_upd);
+int bls381_list_tree_update(bls381_list_tree* tree, size_t n_upd, const uint32_t* indices, size_t off, size_t len,
+                            const uint8_t* values);
+int bls381_list_tree_update_device(bls381_list_tree* tree, size_t n_upd, const uint32_t* d_indices, size_t off,
+                                   size_t len, const uint8_t* d_values, void* d_workspace, void* stream);
+int bls381_list_tree_root(bls381_list_tree* tree, int mix_length, uint8_t root[32]);
+int bls381_list_tree_root_device(bls381_list_tree* tree, int mix_length, uint8_t* d_root32, void* stream);
+int bls381_list_tree_proofs(bls381_list_tree* tree, size_t n_idx, const uint64_t* chunk_indices, uint8_t* proofs,
+                            size_t proof_stride, uint8_t root[32]);
+int bls381_list_tree_proofs_device(bls381_list_tree* tree, size_t n_idx, const uint64_t* d_chunk_indices,
+                                   uint8_t* d_proofs, size_t proof_stride, uint8_t* d_root32, void* stream);
+
 /* ---- committees: the producer of the grouped verify's d_entries ---------- */
 /* get_shuffled_index (0_beacon-chain.md:860-882) for positions first .. first+count-1 of a list of
  * index_count: out[k] = shuffled(first+k), or indices[shuffled(first+k)] when indices != NULL
