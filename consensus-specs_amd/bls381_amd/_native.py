@@ -188,6 +188,29 @@ _SIGS = {
     "bls381_proposer_indices_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p,
                                                       ctypes.c_size_t, ctypes.c_size_t, _u8p, ctypes.c_uint64,
                                                       ctypes.c_uint64, _u8p, _u8p, _u8p]),
+    "bls381_epoch_votes_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t]),
+    "bls381_epoch_votes": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_size_t, ctypes.c_size_t, _u8p,
+                                          ctypes.c_size_t, _u8p, ctypes.c_size_t] + [_u8p] * 16),
+    "bls381_epoch_votes_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_size_t, ctypes.c_size_t, _u8p,
+                                                 ctypes.c_size_t, _u8p, ctypes.c_size_t] + [_u8p] * 18),
+    "bls381_epoch_deltas_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_epoch_deltas": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p, ctypes.c_size_t,
+                                           _u8p, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_uint64, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_epoch_deltas_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p,
+                                                  ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, ctypes.c_size_t, _u8p, _u8p, _u8p,
+                                                  _u8p, ctypes.c_uint64, ctypes.c_uint64, _u8p, _u8p, ctypes.c_uint32, _u8p,
+                                                  _u8p, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_epoch_slashings": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t,
+                                              ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                              ctypes.c_uint64, _u8p]),
+    "bls381_epoch_slashings_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t,
+                                                     ctypes.c_uint64, ctypes.c_uint64, _u8p, ctypes.c_uint64, ctypes.c_uint64,
+                                                     _u8p, _u8p]),
+    "bls381_effective_balances": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                                 ctypes.c_uint64, _u8p, _u8p, _u8p]),
+    "bls381_effective_balances_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                                        ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),
     "bls381_registry_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     "bls381_registry_destroy": (None, [ctypes.c_void_p]),
     "bls381_registry_size": (ctypes.c_size_t, [ctypes.c_void_p]),

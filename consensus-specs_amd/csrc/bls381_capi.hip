@@ -3089,15 +3089,15 @@ int bls381_active_indices_device(size_t n, const uint8_t* d_activation_epoch, co
 // host's would be.
 namespace {
 struct HostFields {
-  static constexpr int MAXF = 3;
+  static constexpr int MAXF = 5;
   const uint8_t* h[MAXF];
-  size_t stride[MAXF];
+  size_t stride[MAXF], width[MAXF];  // width: bytes of one entry (8; 1 for the slashed flag)
   int nf = 0, group[MAXF];           // group: the copy a field travels in
   const uint8_t* lo[MAXF];           // per copy: host range
   size_t bytes[MAXF];
   uint8_t* d[MAXF];                  // per copy: device block (bytes + 8)
   int ncopies = 0;
-  void add(const uint8_t* p, size_t st) { h[nf] = p; stride[nf] = st; ++nf; }
+  void add(const uint8_t* p, size_t st, size_t wd = 8) { h[nf] = p; stride[nf] = st; width[nf] = wd; ++nf; }
   void plan(size_t n) {
     for (int f = 0; f < nf; ++f) {
       group[f] = -1;
@@ -3114,7 +3114,7 @@ struct HostFields {
     }
     for (int f = 0; f < nf; ++f) {
       const int g = group[f];
-      const uint8_t* end = std::max(lo[g] + bytes[g], h[f] + field_span(n, stride[f]));
+      const uint8_t* end = std::max(lo[g] + bytes[g], h[f] + (n ? (n - 1) * stride[f] + width[f] : 0));
       lo[g] = std::min(lo[g], h[f]);
       bytes[g] = (size_t)(end - lo[g]);
     }
@@ -3304,6 +3304,454 @@ int bls381_proposer_indices(size_t n_slots, const uint32_t* committee_off, const
     TRY(bls381_proposer_indices_device(n_slots, committee_off, committee_len, d_sh, n_shuffled, d_bal, balance_stride,
                                        n_validators, seed, epoch, max_effective_balance, d_out, d_ws, hc.s));
     TRY(hc.download(proposer_out, d_out, 4 * n_slots));
+    return hc.finish();
+  });
+}
+
+// ---- epoch rewards: votes, deltas, slashings, hysteresis (bls381_rewards.hpp)
+static bool flag_ok(size_t n, size_t stride) { return stride >= 1 && (n < 2 || stride <= (SIZE_MAX - 1) / (n - 1)); }
+struct VotesWs {
+  votes_committee* cm;
+  votes_att* att;
+  uint8_t* bits;
+  uint64_t* partial;
+};
+static VotesWs carve_votes(Bump& b, size_t n_committees, size_t n_att, size_t bitfield_bytes) {
+  VotesWs w;
+  w.cm = b.take<votes_committee>(n_committees);
+  w.att = b.take<votes_att>(n_att);
+  w.bits = b.take<uint8_t>(bitfield_bytes + 1);
+  w.partial = b.take<uint64_t>(3 * n_committees);
+  return w;
+}
+size_t bls381_epoch_votes_workspace_size(size_t n_committees, size_t n_att, size_t bitfield_bytes) {
+  if (n_committees > (size_t)INT32_MAX || n_att > (size_t)INT32_MAX || bitfield_bytes > 0xFFFFFFFFull) return 0;
+  return carved_bytes([&](Bump& b) { carve_votes(b, n_committees, n_att, bitfield_bytes); });
+}
+
+// The host half of both forms: the slices (inside the shuffled list, disjoint, at most 4,096
+// members), the CSR offsets, verify_bitfield on every bitfield, the flags and the candidate ids.
+static int votes_plan(size_t nc, const uint32_t* coff, const uint32_t* clen, size_t n_shuffled, const uint32_t* att_off,
+                      const uint32_t* bits_off, const uint8_t* bits, const uint8_t* flags, const uint64_t* delay,
+                      const uint32_t* proposer, const uint32_t* cand, const uint32_t* cand_count,
+                      std::vector<votes_committee>& cm, std::vector<votes_att>& att) {
+  if (nc > (size_t)INT32_MAX || (uint64_t)n_shuffled > 0xFFFFFFFFull) return BLS381_EARG;
+  if (nc == 0) return 0;
+  if (!coff || !clen || !att_off || !cand_count) return BLS381_EARG;
+  const size_t n_att = att_off[nc];
+  if (n_att > (size_t)INT32_MAX) return BLS381_EARG;
+  if (n_att && (!bits_off || !flags || !delay || !proposer || !cand)) return BLS381_EARG;
+  cm.resize(nc);
+  att.resize(n_att);
+  std::vector<uint32_t> order(nc);
+  for (size_t c = 0; c < nc; ++c) {
+    if (clen[c] > ATT_MAX_COMMITTEE || (uint64_t)coff[c] + clen[c] > n_shuffled || att_off[c + 1] < att_off[c] ||
+        att_off[c + 1] > n_att)
+      return BLS381_EARG;
+    order[c] = (uint32_t)c;
+    cm[c] = votes_committee{coff[c], clen[c], att_off[c], att_off[c + 1] - att_off[c], cand_count[c]};
+    for (size_t a = att_off[c]; a < att_off[c + 1]; ++a) {
+      if (bits_off[a + 1] < bits_off[a]) return BLS381_EARG;
+      const size_t nbytes = bits_off[a + 1] - bits_off[a];
+      if (nbytes && !bits) return BLS381_EARG;
+      if (nbytes != ((size_t)clen[c] + 7) / 8 || (nbytes && !bitfield_ok(bits + bits_off[a], nbytes, clen[c])))
+        return BLS381_EARG;
+      if (flags[a] > 3 || (cand[a] != VOTES_NONE && cand[a] >= cand_count[c])) return BLS381_EARG;
+      att[a] = votes_att{delay[a], bits_off[a], flags[a], proposer[a], cand[a]};
+    }
+  }
+  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return coff[x] < coff[y]; });
+  uint64_t end = 0;
+  for (size_t k = 0; k < nc; ++k) {
+    const uint32_t c = order[k];
+    if (clen[c] == 0) continue;
+    if (coff[c] < end) return BLS381_EARG;
+    end = (uint64_t)coff[c] + clen[c];
+  }
+  return 0;
+}
+
+int bls381_epoch_votes_device(size_t n_committees, const uint32_t* h_committee_off, const uint32_t* h_committee_len,
+                              const uint32_t* d_shuffled, size_t n_shuffled, size_t n_validators,
+                              const uint8_t* d_slashed, size_t slashed_stride, const uint8_t* d_effective_balance,
+                              size_t stride, const uint32_t* h_att_off, const uint32_t* h_bits_off,
+                              const uint8_t* h_aggregation_bits, const uint8_t* h_att_flags,
+                              const uint64_t* h_att_inclusion_delay, const uint32_t* h_att_proposer,
+                              const uint32_t* h_att_candidate, const uint32_t* h_cand_count, uint32_t* d_votes,
+                              uint64_t* d_incl_delay, uint32_t* d_incl_proposer, uint32_t* d_committee_of,
+                              uint32_t* d_winner, uint64_t* d_winner_balance, uint64_t* d_committee_balance,
+                              uint64_t* d_totals, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n_validators > 0xFFFFFFFFull || !field_ok(n_validators, stride) ||
+        !flag_ok(n_validators, slashed_stride) || !d_totals || !aligned8(d_totals) || !aligned4(d_shuffled) ||
+        !aligned4(d_votes) || !aligned8(d_incl_delay) || !aligned4(d_incl_proposer) || !aligned4(d_committee_of) ||
+        !aligned4(d_winner) || !aligned8(d_winner_balance) || !aligned8(d_committee_balance))
+      return BLS381_EARG;
+    if (n_validators && (!d_slashed || !d_effective_balance || !d_votes || !d_incl_delay || !d_incl_proposer ||
+                         !d_committee_of))
+      return BLS381_EARG;
+    if (n_committees && (!d_winner || !d_winner_balance || !d_committee_balance || !d_workspace ||
+                         (n_shuffled && !d_shuffled)))
+      return BLS381_EARG;
+    std::vector<votes_committee> cm;
+    std::vector<votes_att> att;
+    TRY(votes_plan(n_committees, h_committee_off, h_committee_len, n_shuffled, h_att_off, h_bits_off, h_aggregation_bits,
+                   h_att_flags, h_att_inclusion_delay, h_att_proposer, h_att_candidate, h_cand_count, cm, att));
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 blk(EPOCH_BLOCK);
+    LAUNCH("votes_clear", s, dim3(grid_for(n_validators, EPOCH_BLOCK)), blk, k_votes_clear, (uint64_t)n_validators, d_votes,
+           d_committee_of);
+    if (n_committees == 0) {
+      HIPC(hipMemsetAsync(d_totals, 0, 24, s));
+      return 0;
+    }
+    const size_t n_att = att.size(), bitfield_bytes = n_att ? h_bits_off[n_att] : 0;
+    Bump b(d_workspace, bls381_epoch_votes_workspace_size(n_committees, n_att, bitfield_bytes));
+    const VotesWs w = carve_votes(b, n_committees, n_att, bitfield_bytes);
+    Held<std::vector<votes_committee>> hold_cm(c->keep, s, std::move(cm));
+    Held<std::vector<votes_att>> hold_att(c->keep, s, std::move(att));
+    Held<std::vector<uint8_t>> hold_bits(c->keep, s, std::vector<uint8_t>(bitfield_bytes));
+    if (bitfield_bytes) std::memcpy(hold_bits->data(), h_aggregation_bits, bitfield_bytes);
+    HIPC(hipMemcpyAsync(w.cm, hold_cm->data(), n_committees * sizeof(votes_committee), hipMemcpyHostToDevice, s));
+    if (n_att) HIPC(hipMemcpyAsync(w.att, hold_att->data(), n_att * sizeof(votes_att), hipMemcpyHostToDevice, s));
+    if (bitfield_bytes) HIPC(hipMemcpyAsync(w.bits, hold_bits->data(), bitfield_bytes, hipMemcpyHostToDevice, s));
+    LAUNCH("votes_committees", s, dim3((unsigned)n_committees), blk, k_votes_committees, (const votes_committee*)w.cm,
+           (const votes_att*)w.att, (const uint8_t*)w.bits, d_shuffled, make_u8_field(d_slashed, slashed_stride),
+           make_u64_field(d_effective_balance, stride), (uint64_t)n_validators, d_votes, d_incl_delay, d_incl_proposer,
+           d_committee_of, d_winner, d_winner_balance, d_committee_balance, w.partial);
+    LAUNCH("votes_totals", s, dim3(1), blk, k_votes_totals, n_committees, (const uint64_t*)w.partial, d_totals);
+    return 0;
+  });
+}
+
+int bls381_epoch_votes(size_t n_committees, const uint32_t* committee_off, const uint32_t* committee_len,
+                       const uint32_t* shuffled, size_t n_shuffled, size_t n_validators, const uint8_t* slashed,
+                       size_t slashed_stride, const uint8_t* effective_balance, size_t stride, const uint32_t* att_off,
+                       const uint32_t* bits_off, const uint8_t* aggregation_bits, const uint8_t* att_flags,
+                       const uint64_t* att_inclusion_delay, const uint32_t* att_proposer, const uint32_t* att_candidate,
+                       const uint32_t* cand_count, uint32_t* votes, uint64_t* incl_delay, uint32_t* incl_proposer,
+                       uint32_t* committee_of, uint32_t* winner, uint64_t* winner_balance, uint64_t* committee_balance,
+                       uint64_t totals[3]) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n_validators > 0xFFFFFFFFull || (uint64_t)n_shuffled > 0xFFFFFFFFull ||
+        n_committees > (size_t)INT32_MAX || !field_ok(n_validators, stride) || !flag_ok(n_validators, slashed_stride) ||
+        !totals)
+      return BLS381_EARG;
+    if (n_validators && (!slashed || !effective_balance || !votes || !incl_delay || !incl_proposer || !committee_of))
+      return BLS381_EARG;
+    if (n_committees && (!att_off || !winner || !winner_balance || !committee_balance || (n_shuffled && !shuffled)))
+      return BLS381_EARG;
+    totals[0] = totals[1] = totals[2] = 0;
+    if (n_validators == 0 && n_committees == 0) return 0;
+    const size_t n_att = n_committees ? att_off[n_committees] : 0;
+    if (n_att > (size_t)INT32_MAX || (n_att && !bits_off)) return BLS381_EARG;
+    const size_t bitfield_bytes = n_att ? bits_off[n_att] : 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(slashed, slashed_stride, 1);
+    hf.add(effective_balance, stride);
+    hf.plan(n_validators);
+    const size_t wsb = bls381_epoch_votes_workspace_size(n_committees, n_att, bitfield_bytes);
+    uint32_t *d_sh, *d_votes, *d_prop, *d_cof, *d_win;
+    uint64_t *d_delay, *d_wbal, *d_cbal, *d_tot;
+    uint8_t* d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_sh = b.take<uint32_t>(n_shuffled + 1);
+      d_votes = b.take<uint32_t>(n_validators + 1);
+      d_prop = b.take<uint32_t>(n_validators + 1);
+      d_cof = b.take<uint32_t>(n_validators + 1);
+      d_delay = b.take<uint64_t>(n_validators + 1);
+      d_win = b.take<uint32_t>(n_committees + 1);
+      d_wbal = b.take<uint64_t>(n_committees + 1);
+      d_cbal = b.take<uint64_t>(n_committees + 1);
+      d_tot = b.take<uint64_t>(3);
+      d_ws = b.take<uint8_t>(wsb + 1);
+    }));
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(hc.upload(d_sh, shuffled, 4 * n_shuffled));
+    // entries the call does not write come back as zero
+    if (n_validators) {
+      HIPC(hipMemsetAsync(d_delay, 0, 8 * n_validators, hc.s));
+      HIPC(hipMemsetAsync(d_prop, 0, 4 * n_validators, hc.s));
+    }
+    TRY(bls381_epoch_votes_device(n_committees, committee_off, committee_len, d_sh, n_shuffled, n_validators, hf.dev(0),
+                                  slashed_stride, hf.dev(1), stride, att_off, bits_off, aggregation_bits, att_flags,
+                                  att_inclusion_delay, att_proposer, att_candidate, cand_count, d_votes, d_delay, d_prop,
+                                  d_cof, d_win, d_wbal, d_cbal, d_tot, d_ws, hc.s));
+    TRY(hc.download(votes, d_votes, 4 * n_validators));
+    TRY(hc.download(incl_delay, d_delay, 8 * n_validators));
+    TRY(hc.download(incl_proposer, d_prop, 4 * n_validators));
+    TRY(hc.download(committee_of, d_cof, 4 * n_validators));
+    TRY(hc.download(winner, d_win, 4 * n_committees));
+    TRY(hc.download(winner_balance, d_wbal, 8 * n_committees));
+    TRY(hc.download(committee_balance, d_cbal, 8 * n_committees));
+    TRY(hc.download(totals, d_tot, 24));
+    return hc.finish();
+  });
+}
+
+size_t bls381_epoch_deltas_workspace_size(size_t n) {
+  if ((uint64_t)n > 0xFFFFFFFFull) return 0;
+  return carved_bytes([&](Bump& b) { b.take<uint64_t>(n); });
+}
+static bool deltas_scalars_ok(const bls381_reward_constants* k, uint32_t which, uint64_t previous_epoch,
+                              uint64_t finalized_epoch) {
+  return k && which >= 1 && which <= 3 && previous_epoch != ~(uint64_t)0 && finalized_epoch <= previous_epoch &&
+         k->base_rewards_per_epoch && k->proposer_reward_quotient && k->inactivity_penalty_quotient;
+}
+
+int bls381_epoch_deltas_device(size_t n, const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch,
+                               const uint8_t* d_withdrawable_epoch, const uint8_t* d_effective_balance, size_t stride,
+                               const uint8_t* d_slashed, size_t slashed_stride, const uint32_t* d_votes,
+                               const uint64_t* d_incl_delay, const uint32_t* d_incl_proposer,
+                               const uint32_t* d_committee_of, size_t n_committees, const uint64_t* d_winner_balance,
+                               const uint64_t* d_committee_balance, const uint64_t* d_totals, const uint64_t* d_balances,
+                               uint64_t previous_epoch, uint64_t finalized_epoch, const uint64_t* d_total_balance,
+                               const bls381_reward_constants* constants, uint32_t which, uint64_t* d_rewards,
+                               uint64_t* d_penalties, uint64_t* d_new_balances, uint64_t* d_status, void* d_workspace,
+                               void* stream) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || n_committees > (size_t)INT32_MAX || !field_ok(n, stride) ||
+        !flag_ok(n, slashed_stride) || !deltas_scalars_ok(constants, which, previous_epoch, finalized_epoch) ||
+        !d_total_balance || !d_status || !d_totals || !aligned8(d_total_balance) || !aligned8(d_status) ||
+        !aligned8(d_totals) || !aligned4(d_votes) || !aligned8(d_incl_delay) || !aligned4(d_incl_proposer) ||
+        !aligned4(d_committee_of) || !aligned8(d_winner_balance) || !aligned8(d_committee_balance) ||
+        !aligned8(d_balances) || !aligned8(d_rewards) || !aligned8(d_penalties) || !aligned8(d_new_balances))
+      return BLS381_EARG;
+    if (n && (!d_activation_epoch || !d_exit_epoch || !d_withdrawable_epoch || !d_effective_balance || !d_slashed ||
+              !d_votes || !d_incl_delay || !d_incl_proposer || !d_committee_of || !d_balances || !d_rewards ||
+              !d_penalties || !d_new_balances || !d_workspace))
+      return BLS381_EARG;
+    if (n_committees && (!d_winner_balance || !d_committee_balance)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(hipMemsetAsync(d_status, 0, 8, s));
+    if (n == 0) return 0;
+    Bump b(d_workspace, bls381_epoch_deltas_workspace_size(n));
+    uint64_t* proposer_reward = b.take<uint64_t>(n);
+    HIPC(hipMemsetAsync(proposer_reward, 0, 8 * n, s));
+    deltas_in in;
+    in.activation = make_u64_field(d_activation_epoch, stride);
+    in.exit_ = make_u64_field(d_exit_epoch, stride);
+    in.withdrawable = make_u64_field(d_withdrawable_epoch, stride);
+    in.effective = make_u64_field(d_effective_balance, stride);
+    in.slashed = make_u8_field(d_slashed, slashed_stride);
+    in.votes = d_votes;
+    in.incl_delay = d_incl_delay;
+    in.incl_proposer = d_incl_proposer;
+    in.committee_of = d_committee_of;
+    in.winner_balance = d_winner_balance;
+    in.committee_balance = d_committee_balance;
+    in.totals = d_totals;
+    in.n = n;
+    in.n_committees = n_committees;
+    in.previous_epoch = previous_epoch;
+    in.finalized_epoch = finalized_epoch;
+    in.k = reward_constants{constants->base_reward_factor,
+                            constants->base_rewards_per_epoch,
+                            constants->proposer_reward_quotient,
+                            constants->min_attestation_inclusion_delay,
+                            constants->min_epochs_to_inactivity_penalty,
+                            constants->inactivity_penalty_quotient};
+    in.which = which;
+    const dim3 grid(grid_for(n, EPOCH_BLOCK)), blk(EPOCH_BLOCK);
+    LAUNCH("epoch_deltas", s, grid, blk, k_epoch_deltas, in, d_total_balance, d_rewards, d_penalties,
+           (unsigned long long*)proposer_reward, (unsigned long long*)d_status);
+    LAUNCH("epoch_deltas_apply", s, grid, blk, k_epoch_deltas_apply, (uint64_t)n, d_balances, d_rewards,
+           (const uint64_t*)d_penalties, (const uint64_t*)proposer_reward, d_new_balances, (unsigned long long*)d_status);
+    return 0;
+  });
+}
+
+int bls381_epoch_deltas(size_t n, const uint8_t* activation_epoch, const uint8_t* exit_epoch,
+                        const uint8_t* withdrawable_epoch, const uint8_t* effective_balance, size_t stride,
+                        const uint8_t* slashed, size_t slashed_stride, const uint32_t* votes, const uint64_t* incl_delay,
+                        const uint32_t* incl_proposer, const uint32_t* committee_of, size_t n_committees,
+                        const uint64_t* winner_balance, const uint64_t* committee_balance, const uint64_t totals[3],
+                        const uint64_t* balances, uint64_t previous_epoch, uint64_t finalized_epoch,
+                        uint64_t total_balance, const bls381_reward_constants* constants, uint32_t which,
+                        uint64_t* rewards, uint64_t* penalties, uint64_t* new_balances, uint64_t* overflows_out) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || n_committees > (size_t)INT32_MAX || !field_ok(n, stride) ||
+        !flag_ok(n, slashed_stride) || !deltas_scalars_ok(constants, which, previous_epoch, finalized_epoch) ||
+        !overflows_out || !totals)
+      return BLS381_EARG;
+    if (n && (!activation_epoch || !exit_epoch || !withdrawable_epoch || !effective_balance || !slashed || !votes ||
+              !incl_delay || !incl_proposer || !committee_of || !balances || !rewards || !penalties || !new_balances))
+      return BLS381_EARG;
+    if (n_committees && (!winner_balance || !committee_balance)) return BLS381_EARG;
+    *overflows_out = 0;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(activation_epoch, stride);
+    hf.add(exit_epoch, stride);
+    hf.add(withdrawable_epoch, stride);
+    hf.add(effective_balance, stride);
+    hf.add(slashed, slashed_stride, 1);
+    hf.plan(n);
+    const size_t wsb = bls381_epoch_deltas_workspace_size(n);
+    uint32_t *d_votes, *d_prop, *d_cof;
+    uint64_t *d_delay, *d_wbal, *d_cbal, *d_scal, *d_bal, *d_rew, *d_pen;
+    uint8_t* d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_votes = b.take<uint32_t>(n);
+      d_prop = b.take<uint32_t>(n);
+      d_cof = b.take<uint32_t>(n);
+      d_delay = b.take<uint64_t>(n);
+      d_wbal = b.take<uint64_t>(n_committees + 1);
+      d_cbal = b.take<uint64_t>(n_committees + 1);
+      d_scal = b.take<uint64_t>(5);   // totals[3], the total balance, the status word
+      d_bal = b.take<uint64_t>(n);
+      d_rew = b.take<uint64_t>(n);
+      d_pen = b.take<uint64_t>(n);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    const uint64_t scal[4] = {totals[0], totals[1], totals[2], total_balance};
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(hc.upload(d_votes, votes, 4 * n));
+    TRY(hc.upload(d_prop, incl_proposer, 4 * n));
+    TRY(hc.upload(d_cof, committee_of, 4 * n));
+    TRY(hc.upload(d_delay, incl_delay, 8 * n));
+    TRY(hc.upload(d_wbal, winner_balance, 8 * n_committees));
+    TRY(hc.upload(d_cbal, committee_balance, 8 * n_committees));
+    TRY(hc.upload(d_scal, scal, 32));
+    TRY(hc.upload(d_bal, balances, 8 * n));
+    TRY(bls381_epoch_deltas_device(n, hf.dev(0), hf.dev(1), hf.dev(2), hf.dev(3), stride, hf.dev(4), slashed_stride,
+                                   d_votes, d_delay, d_prop, d_cof, n_committees, d_wbal, d_cbal, d_scal, d_bal,
+                                   previous_epoch, finalized_epoch, d_scal + 3, constants, which, d_rew, d_pen, d_bal,
+                                   d_scal + 4, d_ws, hc.s));
+    TRY(hc.download(rewards, d_rew, 8 * n));
+    TRY(hc.download(penalties, d_pen, 8 * n));
+    TRY(hc.download(new_balances, d_bal, 8 * n));
+    TRY(hc.download(overflows_out, d_scal + 4, 8));
+    return hc.finish();
+  });
+}
+
+int bls381_epoch_slashings_device(size_t n, const uint8_t* d_slashed, size_t slashed_stride,
+                                  const uint8_t* d_withdrawable_epoch, const uint8_t* d_effective_balance, size_t stride,
+                                  uint64_t current_epoch, uint64_t total_penalties, const uint64_t* d_total_balance,
+                                  uint64_t latest_slashed_exit_length, uint64_t min_slashing_penalty_quotient,
+                                  uint64_t* d_balances, void* stream) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || !flag_ok(n, slashed_stride) || !d_total_balance ||
+        !aligned8(d_total_balance) || !aligned8(d_balances) || min_slashing_penalty_quotient == 0)
+      return BLS381_EARG;
+    if (n && (!d_slashed || !d_withdrawable_epoch || !d_effective_balance || !d_balances)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH("epoch_slashings", s, dim3(grid_for(n, EPOCH_BLOCK)), dim3(EPOCH_BLOCK), k_epoch_slashings, (uint64_t)n,
+           make_u8_field(d_slashed, slashed_stride), make_u64_field(d_withdrawable_epoch, stride),
+           make_u64_field(d_effective_balance, stride), current_epoch, total_penalties, d_total_balance,
+           latest_slashed_exit_length, min_slashing_penalty_quotient, d_balances);
+    return 0;
+  });
+}
+
+int bls381_epoch_slashings(size_t n, const uint8_t* slashed, size_t slashed_stride, const uint8_t* withdrawable_epoch,
+                           const uint8_t* effective_balance, size_t stride, uint64_t current_epoch,
+                           uint64_t total_penalties, uint64_t total_balance, uint64_t latest_slashed_exit_length,
+                           uint64_t min_slashing_penalty_quotient, uint64_t* balances) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || !flag_ok(n, slashed_stride) ||
+        min_slashing_penalty_quotient == 0)
+      return BLS381_EARG;
+    if (n && (!slashed || !withdrawable_epoch || !effective_balance || !balances)) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(slashed, slashed_stride, 1);
+    hf.add(withdrawable_epoch, stride);
+    hf.add(effective_balance, stride);
+    hf.plan(n);
+    uint64_t *d_total, *d_bal;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_total = b.take<uint64_t>(1);
+      d_bal = b.take<uint64_t>(n);
+    }));
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(hc.upload(d_total, &total_balance, 8));
+    TRY(hc.upload(d_bal, balances, 8 * n));
+    TRY(bls381_epoch_slashings_device(n, hf.dev(0), slashed_stride, hf.dev(1), hf.dev(2), stride, current_epoch,
+                                      total_penalties, d_total, latest_slashed_exit_length, min_slashing_penalty_quotient,
+                                      d_bal, hc.s));
+    TRY(hc.download(balances, d_bal, 8 * n));
+    return hc.finish();
+  });
+}
+
+int bls381_effective_balances_device(size_t n, const uint64_t* d_balances, const uint8_t* d_effective_balance,
+                                     size_t stride, uint64_t increment, uint64_t max_effective_balance,
+                                     uint32_t* d_indices, uint64_t* d_values, uint64_t* d_changed, void* stream) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || increment == 0 || !d_changed || !aligned8(d_changed) ||
+        !aligned8(d_balances) || !aligned4(d_indices) || !aligned8(d_values))
+      return BLS381_EARG;
+    if (n && (!d_balances || !d_effective_balance || !d_indices || !d_values)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(hipMemsetAsync(d_changed, 0, 8, s));
+    LAUNCH("effective_balances", s, dim3(grid_for(n, EPOCH_BLOCK)), dim3(EPOCH_BLOCK), k_effective_balances, (uint64_t)n,
+           d_balances, make_u64_field(d_effective_balance, stride), increment, max_effective_balance, d_indices, d_values,
+           (unsigned long long*)d_changed);
+    return 0;
+  });
+}
+
+int bls381_effective_balances(size_t n, const uint64_t* balances, const uint8_t* effective_balance, size_t stride,
+                              uint64_t increment, uint64_t max_effective_balance, uint32_t* indices, uint64_t* values,
+                              uint64_t* changed_out) {
+  return guarded([&]() -> int {
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || increment == 0 || !changed_out) return BLS381_EARG;
+    if (n && (!balances || !effective_balance || !indices || !values)) return BLS381_EARG;
+    *changed_out = 0;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(effective_balance, stride);
+    hf.plan(n);
+    uint64_t *d_bal, *d_val, *d_changed;
+    uint32_t* d_idx;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_bal = b.take<uint64_t>(n);
+      d_val = b.take<uint64_t>(n);
+      d_idx = b.take<uint32_t>(n);
+      d_changed = b.take<uint64_t>(1);
+    }));
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(hc.upload(d_bal, balances, 8 * n));
+    TRY(bls381_effective_balances_device(n, d_bal, hf.dev(0), stride, increment, max_effective_balance, d_idx, d_val,
+                                         d_changed, hc.s));
+    TRY(hc.download(indices, d_idx, 4 * n));
+    TRY(hc.download(values, d_val, 8 * n));
+    TRY(hc.download(changed_out, d_changed, 8));
     return hc.finish();
   });
 }

@@ -17,6 +17,7 @@
 #include "bls381_listtree.hpp"
 #include "bls381_shuffle.hpp"
 #include "bls381_epoch.hpp"
+#include "bls381_rewards.hpp"
 #include "bls381_keytable.hpp"
 
 namespace bls381 {
@@ -2280,6 +2281,130 @@ __global__ void __launch_bounds__(EPOCH_BLOCK) k_proposers(const proposer_slot* 
     }
   }
   if (tid == 0) proposer[blockIdx.x] = PROPOSER_NONE;
+}
+
+// ------------------------------ epoch rewards: votes, deltas, slashings, hysteresis (§7g) -------
+// (the per-item functions and the committee walk: bls381_rewards.hpp)
+// validators in no committee: votes 0, committee VOTES_NONE
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_votes_clear(uint64_t n, uint32_t* __restrict__ votes,
+                                                             uint32_t* __restrict__ committee_of) {
+  const uint64_t i = (uint64_t)blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  votes[i] = 0;
+  committee_of[i] = VOTES_NONE;
+}
+
+// committee blockIdx.x: its members' votes and inclusion facts, its winner and balances
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_votes_committees(const votes_committee* __restrict__ committees,
+                                                                  const votes_att* __restrict__ atts,
+                                                                  const uint8_t* __restrict__ bits,
+                                                                  const uint32_t* __restrict__ shuffled, u8_field slashed,
+                                                                  u64_field effective, uint64_t n_validators,
+                                                                  uint32_t* votes, uint64_t* __restrict__ incl_delay,
+                                                                  uint32_t* __restrict__ incl_proposer,
+                                                                  uint32_t* __restrict__ committee_of,
+                                                                  uint32_t* __restrict__ winner,
+                                                                  uint64_t* __restrict__ winner_balance,
+                                                                  uint64_t* __restrict__ committee_balance,
+                                                                  uint64_t* __restrict__ partial) {
+  __shared__ votes_lds lds;
+  const votes_committee cm = committees[blockIdx.x];
+  votes_walk(&lds, threadIdx.x, EPOCH_BLOCK, wg_sync{}, blockIdx.x, cm, shuffled, atts, bits, slashed, effective,
+             n_validators, votes, incl_delay, incl_proposer, committee_of, winner, winner_balance, committee_balance,
+             partial);
+}
+
+// one workgroup: totals[g] = the sum of partial[3 c + g] over the committees
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_votes_totals(size_t n_committees, const uint64_t* __restrict__ partial,
+                                                              uint64_t* __restrict__ totals) {
+  __shared__ uint64_t red[EPOCH_BLOCK];
+  for (uint32_t g = 0; g < 3; ++g) {
+    uint64_t x = 0;
+    for (size_t c = threadIdx.x; c < n_committees; c += EPOCH_BLOCK) x += partial[3 * c + g];
+    const uint64_t sum = votes_reduce(red, threadIdx.x, EPOCH_BLOCK, wg_sync{}, x);
+    if (threadIdx.x == 0) totals[g] = sum;
+  }
+}
+
+// validator i's own rewards and penalties; its proposer's micro-reward goes to proposer_reward
+// (zeroed before the launch) by a 64-bit atomic add: fewer than 2^32 addends below 2^32 cannot wrap
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_epoch_deltas(deltas_in in, const uint64_t* __restrict__ total_balance,
+                                                              uint64_t* __restrict__ rewards,
+                                                              uint64_t* __restrict__ penalties,
+                                                              unsigned long long* proposer_reward,
+                                                              unsigned long long* status) {
+  const uint64_t i = (uint64_t)blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (i >= in.n) return;
+  const uint64_t total = floor_one(*total_balance);
+  const validator_delta d = validator_deltas(in, total, isqrt_u64(total), (size_t)i);
+  rewards[i] = d.reward;
+  penalties[i] = d.penalty;
+  if (d.proposer != VOTES_NONE && d.proposer_addend) atomicAdd(proposer_reward + d.proposer, (unsigned long long)d.proposer_addend);
+  if (d.overflows) atomicAdd(status, (unsigned long long)d.overflows);
+}
+
+// rewards[i] += what the proposers' scatter brought; new_balances[i] = increase_balance then
+// decrease_balance (new_balances may be balances: lane i reads entry i before it writes it)
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_epoch_deltas_apply(uint64_t n, const uint64_t* balances,
+                                                                    uint64_t* __restrict__ rewards,
+                                                                    const uint64_t* __restrict__ penalties,
+                                                                    const uint64_t* __restrict__ proposer_reward,
+                                                                    uint64_t* new_balances, unsigned long long* status) {
+  const uint64_t i = (uint64_t)blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  uint32_t ovf = 0;
+  uint64_t reward;
+  const uint64_t nb = apply_deltas(balances[i], rewards[i], proposer_reward[i], penalties[i], &reward, &ovf);
+  rewards[i] = reward;
+  new_balances[i] = nb;
+  if (ovf) atomicAdd(status, (unsigned long long)ovf);
+}
+
+// process_slashings over balances in place
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_epoch_slashings(uint64_t n, u8_field slashed, u64_field withdrawable,
+                                                                 u64_field effective, uint64_t current_epoch,
+                                                                 uint64_t total_penalties,
+                                                                 const uint64_t* __restrict__ total_balance,
+                                                                 uint64_t latest_slashed_exit_length,
+                                                                 uint64_t min_slashing_penalty_quotient,
+                                                                 uint64_t* __restrict__ balances) {
+  const uint64_t i = (uint64_t)blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  if (!flag_load(slashed, (size_t)i)) return;
+  const uint64_t penalty = slashing_penalty(true, field_load(withdrawable, (size_t)i), field_load(effective, (size_t)i),
+                                            current_epoch, total_penalties, floor_one(*total_balance),
+                                            latest_slashed_exit_length, min_slashing_penalty_quotient);
+  if (penalty) {
+    const uint64_t b = balances[i];
+    balances[i] = b > penalty ? b - penalty : 0;
+  }
+}
+
+// the hysteresis: indices[i] = i and values[i] = the new effective balance where it changes,
+// 0xFFFFFFFF and the old value where it does not; one atomic add per workgroup with a change into
+// *changed (one per wave serialises: 16,384 adds to one address took 0.2 ms at 2^20 validators)
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_effective_balances(uint64_t n, const uint64_t* __restrict__ balances,
+                                                                    u64_field effective, uint64_t increment,
+                                                                    uint64_t max_effective_balance,
+                                                                    uint32_t* __restrict__ indices,
+                                                                    uint64_t* __restrict__ values,
+                                                                    unsigned long long* changed) {
+  const uint64_t i = (uint64_t)blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  bool moved = false;
+  if (i < n) {
+    uint64_t v;
+    moved = effective_balance_update(balances[i], field_load(effective, (size_t)i), increment, max_effective_balance, &v);
+    indices[i] = moved ? (uint32_t)i : VOTES_NONE;
+    values[i] = v;
+  }
+  __shared__ uint32_t wave_moved[EPOCH_BLOCK / 64];
+  const uint64_t m = __ballot(moved);
+  if ((threadIdx.x & 63u) == 0) wave_moved[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t c = wave_moved[0] + wave_moved[1] + wave_moved[2] + wave_moved[3];
+    if (c) atomicAdd(changed, (unsigned long long)c);
+  }
 }
 
 }  // namespace bls381

@@ -736,6 +736,155 @@ int bls381_proposer_indices_device(size_t n_slots, const uint32_t* h_committee_o
                                    uint64_t max_effective_balance, uint32_t* d_proposer_out, void* d_workspace,
                                    void* stream);
 
+/* ---- epoch rewards: votes, deltas, slashings and the hysteresis ------------ */
+/* The whole-registry work of process_epoch over the records where they are (DESIGN.md section
+ * 7g): process_rewards_and_penalties (0_beacon-chain.md:1389-1475), process_slashings (:1505-1524)
+ * and the hysteresis of process_final_updates (:1535-1540).  All results are the spec's integers.
+ * Validator fields are little-endian uint64 at base + i * stride as in the epoch context (one
+ * `stride` for all uint64 fields of a call: 121 with bases records + 88 / 96 / 104 / 113 for
+ * activation_epoch / exit_epoch / withdrawable_epoch / effective_balance, or 8 over plain arrays);
+ * the slashed flag is one byte at slashed + i * slashed_stride (records + 112 with stride 121, or
+ * stride 1 over a plain array; any non-zero byte is slashed).  Balances, rewards, penalties and
+ * values are plain uint64 arrays, 8-byte aligned.
+ *
+ * bls381_epoch_votes: the PendingAttestations of one epoch (previous or current) as per-validator
+ * facts and per-committee crosslink results.  Committee c is shuffled[committee_off[c] .. +
+ * committee_len[c]) (at most 4,096 members; the slices lie inside n_shuffled and do not overlap,
+ * and the shuffled list is a permutation, so a validator sits in at most one committee).  Its
+ * attestations are att_off[c] .. att_off[c+1] - 1 (n_committees + 1 entries, n_att =
+ * att_off[n_committees]), in the order they have in the state list.  Attestation a has its
+ * aggregation bitfield at bytes [bits_off[a], bits_off[a+1]) of aggregation_bits, att_flags[a]
+ * (bit 0: matching target, bit 1: matching head; the caller has compared the roots),
+ * att_inclusion_delay[a], att_proposer[a] and att_candidate[a]: 0 .. cand_count[c] - 1, the
+ * crosslink candidate of its committee it votes for, or 0xFFFFFFFF for none.  The host half runs
+ * verify_bitfield (:970-982) on every bitfield.  Outputs:
+ *   votes[i]           bit 0: i attests in some attestation (source), bit 1: in one with the
+ *                      target flag, bit 2: in one with the head flag, bit 3: in an attestation of
+ *                      its committee's winning candidate, bit 4: member of a committee.  Bits 0-3
+ *                      only for slashed == 0 (get_unslashed_attesting_indices, :1294-1300); 0 for
+ *                      a validator in no committee.  All n_validators words are written.
+ *   incl_delay[i], incl_proposer[i]   for i with bit 0: inclusion_delay and proposer_index of the
+ *                      attestation min(..., key=inclusion_delay) picks (:1424-1427): the smallest
+ *                      delay, among equals the first in list order.  Other entries are not written.
+ *   committee_of[i]    i's committee, or 0xFFFFFFFF.  All n_validators words are written.
+ *   winner[c], winner_balance[c], committee_balance[c]   the candidate with the largest attesting
+ *                      balance (the sum of effective_balance over the unslashed members of the
+ *                      union of its attestations), among equals the largest id, or 0xFFFFFFFF with
+ *                      balance 0 when cand_count[c] == 0; the sum over all members.  Unfloored.
+ *   totals[0..2]       the sums of effective_balance over the validators with bit 0, 1 and 2:
+ *                      get_attesting_balance of the matching source / target / head attestations
+ *                      without its floor of 1.  64-bit sums.
+ * A member at or above n_validators is passed over.  The device form takes the committee and
+ * attestation arrays as host memory and the shuffled list and the fields as device memory, copies
+ * the descriptors and bitfields into the workspace (bls381_epoch_votes_workspace_size(
+ * n_committees, n_att, bits_off[n_att])) and writes d_totals (3 entries).
+ *
+ * bls381_epoch_deltas: get_attestation_deltas (which & 1) and get_crosslink_deltas (which & 2)
+ * over the outputs of bls381_epoch_votes for the previous epoch, and their application:
+ * rewards[i] and penalties[i] are the sums of the chosen kinds, new_balances[i] =
+ * decrease_balance(increase_balance(balances[i], rewards[i]), penalties[i]) (saturating at 0);
+ * new_balances may be balances.  total_balance is get_total_active_balance of the current epoch
+ * (floored at 1 here); in the device form it is a device pointer, d_count_and_total + 1 of
+ * bls381_active_indices_device, and the host reads nothing back.  integer_squareroot is computed
+ * on the device, exactly.  eligible = active at previous_epoch, or slashed with previous_epoch + 1
+ * < withdrawable_epoch; the inclusion rewards go to every validator with bit 0; the inactivity
+ * branch runs when previous_epoch - finalized_epoch > min_epochs_to_inactivity_penalty.
+ * Overflows: products go through a 128-bit product; a quotient of 2^64 or more, a per-validator
+ * sum that wraps and an increase_balance that wraps saturate at 2^64 - 1 and each adds 1 to the
+ * status word; a proposer micro-reward of 2^32 or more, an incl_proposer at or above n, an
+ * incl_delay of 0 (with bit 0) and a committee_of at or above n_committees (other than
+ * 0xFFFFFFFF) add nothing and each adds 1.  The host form returns the count in *overflows_out;
+ * the device form zeroes and then counts in *d_status (uint64).  Workspace:
+ * bls381_epoch_deltas_workspace_size(n).
+ *
+ * bls381_epoch_slashings: process_slashings over balances in place: for slashed validators with
+ * current_epoch == withdrawable_epoch - latest_slashed_exit_length / 2 the penalty
+ * max(effective_balance * min(3 total_penalties, total_balance) / total_balance,
+ * effective_balance / min_slashing_penalty_quotient), none of whose terms wraps; total_penalties
+ * is the caller's difference of latest_slashed_balances, total_balance as above.
+ *
+ * bls381_effective_balances: the hysteresis.  indices[i] = i where validator i's effective
+ * balance changes (balance < effective_balance or effective_balance + 3 (increment / 2) <
+ * balance, compared without wrapping, and the new value min(balance - balance % increment,
+ * max_effective_balance) differs) and 0xFFFFFFFF where it does not; values[i] = the new (or
+ * unchanged) value; *changed = how many changed.  bls381_list_tree_update_device takes the two
+ * arrays as they are (off = 113, len = 8, n_upd = n): it skips 0xFFFFFFFF.
+ *
+ * BLS381_EARG: n, n_validators or n_shuffled above 2^32 - 1, n_committees or n_att above 2^31 - 1;
+ * a stride below 8 or a slashed_stride of 0; a NULL argument that is needed (fields, inputs and
+ * outputs when the count of items is not 0; constants, total_balance, overflows_out / d_status,
+ * changed_out / d_changed and d_totals always; the workspace of a device form whose size is not
+ * 0); uint64 arrays not 8-byte or uint32 arrays not 4-byte aligned in the device forms; a
+ * committee longer than 4,096, outside n_shuffled or overlapping another; descending att_off or
+ * bits_off; a bitfield that fails verify_bitfield; att_flags above 3; a candidate that is neither
+ * 0xFFFFFFFF nor below its committee's cand_count; which outside 1..3; previous_epoch of 2^64 - 1
+ * or below finalized_epoch; base_rewards_per_epoch, proposer_reward_quotient,
+ * inactivity_penalty_quotient, min_slashing_penalty_quotient or increment of 0.  A count of 0 is
+ * BLS381_OK and runs no kernel (the scalar outputs are written as 0).  Host-pointer forms stage,
+ * run on the engine's stream and return synchronised; device forms are queued on `stream`, never
+ * synchronise and read nothing back. */
+typedef struct bls381_reward_constants {
+  uint64_t base_reward_factor;
+  uint64_t base_rewards_per_epoch;
+  uint64_t proposer_reward_quotient;
+  uint64_t min_attestation_inclusion_delay;
+  uint64_t min_epochs_to_inactivity_penalty;
+  uint64_t inactivity_penalty_quotient;
+} bls381_reward_constants;
+size_t bls381_epoch_votes_workspace_size(size_t n_committees, size_t n_att, size_t bitfield_bytes);
+int bls381_epoch_votes(size_t n_committees, const uint32_t* committee_off, const uint32_t* committee_len,
+                       const uint32_t* shuffled, size_t n_shuffled, size_t n_validators, const uint8_t* slashed,
+                       size_t slashed_stride, const uint8_t* effective_balance, size_t stride, const uint32_t* att_off,
+                       const uint32_t* bits_off, const uint8_t* aggregation_bits, const uint8_t* att_flags,
+                       const uint64_t* att_inclusion_delay, const uint32_t* att_proposer, const uint32_t* att_candidate,
+                       const uint32_t* cand_count, uint32_t* votes, uint64_t* incl_delay, uint32_t* incl_proposer,
+                       uint32_t* committee_of, uint32_t* winner, uint64_t* winner_balance, uint64_t* committee_balance,
+                       uint64_t totals[3]);
+int bls381_epoch_votes_device(size_t n_committees, const uint32_t* h_committee_off, const uint32_t* h_committee_len,
+                              const uint32_t* d_shuffled, size_t n_shuffled, size_t n_validators,
+                              const uint8_t* d_slashed, size_t slashed_stride, const uint8_t* d_effective_balance,
+                              size_t stride, const uint32_t* h_att_off, const uint32_t* h_bits_off,
+                              const uint8_t* h_aggregation_bits, const uint8_t* h_att_flags,
+                              const uint64_t* h_att_inclusion_delay, const uint32_t* h_att_proposer,
+                              const uint32_t* h_att_candidate, const uint32_t* h_cand_count, uint32_t* d_votes,
+                              uint64_t* d_incl_delay, uint32_t* d_incl_proposer, uint32_t* d_committee_of,
+                              uint32_t* d_winner, uint64_t* d_winner_balance, uint64_t* d_committee_balance,
+                              uint64_t* d_totals, void* d_workspace, void* stream);
+size_t bls381_epoch_deltas_workspace_size(size_t n);
+int bls381_epoch_deltas(size_t n, const uint8_t* activation_epoch, const uint8_t* exit_epoch,
+                        const uint8_t* withdrawable_epoch, const uint8_t* effective_balance, size_t stride,
+                        const uint8_t* slashed, size_t slashed_stride, const uint32_t* votes, const uint64_t* incl_delay,
+                        const uint32_t* incl_proposer, const uint32_t* committee_of, size_t n_committees,
+                        const uint64_t* winner_balance, const uint64_t* committee_balance, const uint64_t totals[3],
+                        const uint64_t* balances, uint64_t previous_epoch, uint64_t finalized_epoch,
+                        uint64_t total_balance, const bls381_reward_constants* constants, uint32_t which,
+                        uint64_t* rewards, uint64_t* penalties, uint64_t* new_balances, uint64_t* overflows_out);
+int bls381_epoch_deltas_device(size_t n, const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch,
+                               const uint8_t* d_withdrawable_epoch, const uint8_t* d_effective_balance, size_t stride,
+                               const uint8_t* d_slashed, size_t slashed_stride, const uint32_t* d_votes,
+                               const uint64_t* d_incl_delay, const uint32_t* d_incl_proposer,
+                               const uint32_t* d_committee_of, size_t n_committees, const uint64_t* d_winner_balance,
+                               const uint64_t* d_committee_balance, const uint64_t* d_totals, const uint64_t* d_balances,
+                               uint64_t previous_epoch, uint64_t finalized_epoch, const uint64_t* d_total_balance,
+                               const bls381_reward_constants* constants, uint32_t which, uint64_t* d_rewards,
+                               uint64_t* d_penalties, uint64_t* d_new_balances, uint64_t* d_status, void* d_workspace,
+                               void* stream);
+int bls381_epoch_slashings(size_t n, const uint8_t* slashed, size_t slashed_stride, const uint8_t* withdrawable_epoch,
+                           const uint8_t* effective_balance, size_t stride, uint64_t current_epoch,
+                           uint64_t total_penalties, uint64_t total_balance, uint64_t latest_slashed_exit_length,
+                           uint64_t min_slashing_penalty_quotient, uint64_t* balances);
+int bls381_epoch_slashings_device(size_t n, const uint8_t* d_slashed, size_t slashed_stride,
+                                  const uint8_t* d_withdrawable_epoch, const uint8_t* d_effective_balance, size_t stride,
+                                  uint64_t current_epoch, uint64_t total_penalties, const uint64_t* d_total_balance,
+                                  uint64_t latest_slashed_exit_length, uint64_t min_slashing_penalty_quotient,
+                                  uint64_t* d_balances, void* stream);
+int bls381_effective_balances(size_t n, const uint64_t* balances, const uint8_t* effective_balance, size_t stride,
+                              uint64_t increment, uint64_t max_effective_balance, uint32_t* indices, uint64_t* values,
+                              uint64_t* changed_out);
+int bls381_effective_balances_device(size_t n, const uint64_t* d_balances, const uint8_t* d_effective_balance,
+                                     size_t stride, uint64_t increment, uint64_t max_effective_balance,
+                                     uint32_t* d_indices, uint64_t* d_values, uint64_t* d_changed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
