@@ -211,6 +211,15 @@ _SIGS = {
                                                  ctypes.c_uint64, _u8p, _u8p, _u8p]),
     "bls381_effective_balances_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                         ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_registry_updates_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_registry_updates": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_size_t,
+                                               ctypes.c_uint64, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_registry_updates_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_size_t,
+                                                      ctypes.c_uint64, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p, _u8p,
+                                                      _u8p]),
+    "bls381_exit_queue": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64, _u8p, _u8p]),
+    "bls381_exit_queue_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64, _u8p,
+                                                _u8p, _u8p, _u8p]),
     "bls381_registry_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     "bls381_registry_destroy": (None, [ctypes.c_void_p]),
     "bls381_registry_size": (ctypes.c_size_t, [ctypes.c_void_p]),

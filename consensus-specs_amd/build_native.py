@@ -20,7 +20,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_SOURCES = ["bls381_capi.hip"]
 HEADERS = ["bls381_defs.hpp", "bls381_consts.hpp", "bls381_field.hpp", "bls381_curve.hpp", "bls381_hash.hpp",
            "bls381_lazy.hpp", "bls381_pairing.hpp", "bls381_pair.hpp", "bls381_quad.hpp", "bls381_ssz.hpp",
-           "bls381_merkle.hpp", "bls381_deptree.hpp", "bls381_listtree.hpp", "bls381_shuffle.hpp", "bls381_epoch.hpp", "bls381_rewards.hpp", "bls381_keytable.hpp", "bls381_plan.hpp", "bls381_scope.hpp", "bls381_kernels.hpp"]
+           "bls381_merkle.hpp", "bls381_deptree.hpp", "bls381_listtree.hpp", "bls381_shuffle.hpp", "bls381_epoch.hpp", "bls381_rewards.hpp", "bls381_regupd.hpp", "bls381_keytable.hpp", "bls381_plan.hpp", "bls381_scope.hpp", "bls381_kernels.hpp"]
 
 
 def _newer(target, deps):
@@ -113,7 +113,7 @@ def build_hostcheck(force=False, sanitize=False, count_ops=False, defines=()):
         os.makedirs(SANITIZE_DIR, exist_ok=True)
     out = os.path.join(SANITIZE_DIR if (sanitize or defines) else LIB, name)
     src = os.path.join(CSRC, "host_check.cpp")
-    deps = [src, os.path.join(CSRC, "host_check_rewards.hpp")] + [
+    deps = [src, os.path.join(CSRC, "host_check_rewards.hpp"), os.path.join(CSRC, "host_check_regupd.hpp")] + [
         os.path.join(CSRC, f) for f in HEADERS if f != "bls381_kernels.hpp"]
     if not force and _newer(out, deps):
         return out
@@ -141,6 +141,22 @@ def build_rewards_check(force=False):
     # the sanitizer runtimes are linked into the program: it runs whatever else the loader brings
     _run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
           "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, src, "-o", out])
+    return out
+
+
+def build_regupd_check(force=False):
+    """The stand-alone ASan/UBSan program over csrc/bls381_regupd.hpp (csrc/regupd_check_main.cpp,
+    its own main; tests/test_registry_updates_host.py runs it).  Out of tree like the sanitized library."""
+    os.makedirs(SANITIZE_DIR, exist_ok=True)
+    out = os.path.join(SANITIZE_DIR, "regupd_check_asan")
+    src = os.path.join(CSRC, "regupd_check_main.cpp")
+    deps = [src] + [os.path.join(CSRC, f) for f in (
+        "host_check_regupd.hpp", "bls381_regupd.hpp", "bls381_epoch.hpp", "bls381_shuffle.hpp", "bls381_defs.hpp")]
+    if not force and _newer(out, deps):
+        return out
+    _run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+          "-static-libasan", "-static-libubsan", "-pthread", "-fno-omit-frame-pointer", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, src,
+          "-o", out])
     return out
 
 

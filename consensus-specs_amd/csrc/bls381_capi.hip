@@ -3756,6 +3756,215 @@ int bls381_effective_balances(size_t n, const uint64_t* balances, const uint8_t*
   });
 }
 
+// ---- registry updates: ejections, exit queue, activations (bls381_regupd.hpp)
+struct RegupdWs {
+  uint64_t *ballots_ejected, *ballots_candidate, *tile_peak_epoch, *sc, *keys;
+  uint32_t *tile_count, *tile_peak_count, *offset_ejected, *offset_candidate, *cand_index, *hist;
+};
+static RegupdWs carve_regupd(Bump& b, size_t n) {
+  const size_t tiles = active_tiles(n);
+  RegupdWs w;
+  w.ballots_ejected = b.take<uint64_t>(tiles * ACTIVE_TILE_BALLOTS);
+  w.ballots_candidate = b.take<uint64_t>(tiles * ACTIVE_TILE_BALLOTS);
+  w.tile_peak_epoch = b.take<uint64_t>(tiles);
+  w.sc = b.take<uint64_t>(RU_SCALARS);
+  w.keys = b.take<uint64_t>(n);
+  w.tile_count = b.take<uint32_t>(3 * tiles);
+  w.tile_peak_count = b.take<uint32_t>(tiles);
+  w.offset_ejected = b.take<uint32_t>(tiles);
+  w.offset_candidate = b.take<uint32_t>(tiles);
+  w.cand_index = b.take<uint32_t>(n);
+  w.hist = b.take<uint32_t>((size_t)REGUPD_DIGITS * REGUPD_BINS);
+  return w;
+}
+size_t bls381_registry_updates_workspace_size(size_t n) {
+  if ((uint64_t)n > 0xFFFFFFFFull) return 0;
+  return carved_bytes([&](Bump& b) { carve_regupd(b, n); });
+}
+
+// the constants and the two delayed epochs of a call, or false for arguments it rejects
+static bool regupd_scalars_ok(size_t n, const bls381_registry_constants* constants, uint64_t current_epoch,
+                              const uint64_t* finalized_epoch, registry_constants* kc, regupd_epochs* e) {
+  if (!constants || constants->churn_limit_quotient == 0) return false;
+  *kc = registry_constants{constants->max_effective_balance,      constants->ejection_balance,
+                           constants->activation_exit_delay,      constants->min_validator_withdrawability_delay,
+                           constants->min_per_epoch_churn_limit,  constants->churn_limit_quotient};
+  // at most n validators are active: a limit of 0 that the arguments alone show
+  if (kc->min_per_epoch_churn_limit == 0 && (uint64_t)n / kc->churn_limit_quotient == 0) return false;
+  e->cur = current_epoch;
+  e->delayed_fin = 0;
+  if (!delayed_epoch(current_epoch, kc->activation_exit_delay, &e->delayed_cur)) return false;
+  if (finalized_epoch && !delayed_epoch(*finalized_epoch, kc->activation_exit_delay, &e->delayed_fin)) return false;
+  return true;
+}
+
+int bls381_exit_queue_device(size_t n, const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch, size_t stride,
+                             uint64_t current_epoch, const bls381_registry_constants* constants, uint64_t* d_queue,
+                             void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    registry_constants kc;
+    regupd_epochs e;
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || !d_queue || !aligned8(d_queue) || !d_workspace ||
+        !regupd_scalars_ok(n, constants, current_epoch, nullptr, &kc, &e))
+      return BLS381_EARG;
+    if (n && (!d_activation_epoch || !d_exit_epoch)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_registry_updates_workspace_size(n));
+    const RegupdWs w = carve_regupd(b, n);
+    const size_t tiles = active_tiles(n);
+    const dim3 blk(EPOCH_BLOCK);
+    const u64_field act = make_u64_field(d_activation_epoch, stride), ext = make_u64_field(d_exit_epoch, stride);
+    const regupd_fields f{act, act, ext, ext, act};   // queue_only reads activation and exit alone
+    if (tiles)
+      LAUNCH("regupd_count", s, dim3((unsigned)tiles), blk, k_regupd_count, (uint64_t)n, f, e, kc, 1, w.ballots_ejected,
+             w.ballots_candidate, w.tile_count, w.tile_peak_epoch, w.tile_peak_count);
+    LAUNCH("regupd_scan", s, dim3(1), blk, k_regupd_scan, tiles, (const uint32_t*)w.tile_count,
+           (const uint64_t*)w.tile_peak_epoch, (const uint32_t*)w.tile_peak_count, w.offset_ejected, w.offset_candidate, kc,
+           e.delayed_cur, w.sc, (uint64_t*)nullptr, d_queue);
+    return 0;
+  });
+}
+
+int bls381_exit_queue(size_t n, const uint8_t* activation_epoch, const uint8_t* exit_epoch, size_t stride,
+                      uint64_t current_epoch, const bls381_registry_constants* constants, uint64_t queue_out[4]) {
+  return guarded([&]() -> int {
+    registry_constants kc;
+    regupd_epochs e;
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || !queue_out ||
+        !regupd_scalars_ok(n, constants, current_epoch, nullptr, &kc, &e))
+      return BLS381_EARG;
+    if (n && (!activation_epoch || !exit_epoch)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(activation_epoch, stride);
+    hf.add(exit_epoch, stride);
+    hf.plan(n);
+    const size_t wsb = bls381_registry_updates_workspace_size(n);
+    uint64_t* d_queue;
+    uint8_t* d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_queue = b.take<uint64_t>(4);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(bls381_exit_queue_device(n, hf.dev(0), hf.dev(1), stride, current_epoch, constants, d_queue, d_ws, hc.s));
+    uint64_t q[4];
+    TRY(hc.download(q, d_queue, 32));
+    TRY(hc.finish());
+    if (q[2] == 0) return BLS381_EARG;   // no minimum and too few active validators: no churn limit
+    for (int x = 0; x < 4; ++x) queue_out[x] = q[x];
+    return 0;
+  });
+}
+
+int bls381_registry_updates_device(size_t n, const uint8_t* d_activation_eligibility_epoch,
+                                   const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch,
+                                   const uint8_t* d_withdrawable_epoch, const uint8_t* d_effective_balance, size_t stride,
+                                   uint64_t current_epoch, uint64_t finalized_epoch,
+                                   const bls381_registry_constants* constants, uint32_t* d_indices, uint8_t* d_values,
+                                   uint64_t* d_summary, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    registry_constants kc;
+    regupd_epochs e;
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || !d_summary || !aligned8(d_summary) || !d_workspace ||
+        !aligned4(d_indices) || !aligned8(d_values) ||
+        !regupd_scalars_ok(n, constants, current_epoch, &finalized_epoch, &kc, &e))
+      return BLS381_EARG;
+    if (n && (!d_activation_eligibility_epoch || !d_activation_epoch || !d_exit_epoch || !d_withdrawable_epoch ||
+              !d_effective_balance || !d_indices || !d_values))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Bump b(d_workspace, bls381_registry_updates_workspace_size(n));
+    const RegupdWs w = carve_regupd(b, n);
+    const size_t tiles = active_tiles(n);
+    const dim3 blk(EPOCH_BLOCK), grid((unsigned)tiles);
+    const regupd_fields f{make_u64_field(d_activation_eligibility_epoch, stride), make_u64_field(d_activation_epoch, stride),
+                          make_u64_field(d_exit_epoch, stride), make_u64_field(d_withdrawable_epoch, stride),
+                          make_u64_field(d_effective_balance, stride)};
+    HIPC(hipMemsetAsync(d_summary, 0, 8 * RS_WORDS, s));
+    if (tiles)
+      LAUNCH("regupd_count", s, grid, blk, k_regupd_count, (uint64_t)n, f, e, kc, 0, w.ballots_ejected,
+             w.ballots_candidate, w.tile_count, w.tile_peak_epoch, w.tile_peak_count);
+    LAUNCH("regupd_scan", s, dim3(1), blk, k_regupd_scan, tiles, (const uint32_t*)w.tile_count,
+           (const uint64_t*)w.tile_peak_epoch, (const uint32_t*)w.tile_peak_count, w.offset_ejected, w.offset_candidate, kc,
+           e.delayed_cur, w.sc, d_summary, (uint64_t*)nullptr);
+    if (n == 0) return 0;
+    HIPC(hipMemsetAsync(w.hist, 0, 4 * (size_t)REGUPD_DIGITS * REGUPD_BINS, s));
+    LAUNCH("regupd_compact", s, grid, blk, k_regupd_compact, (const uint64_t*)w.ballots_candidate,
+           (const uint32_t*)w.offset_candidate, f.eligibility, f.effective, e.cur, kc.max_effective_balance, w.keys,
+           w.cand_index);
+    // the grid covers n entries; the workgroups past the K candidates leave at once
+    for (uint32_t pass = 0; pass <= REGUPD_DIGITS; ++pass)
+      LAUNCH("regupd_select", s, pass < REGUPD_DIGITS ? grid : dim3(1), blk, k_regupd_select, pass,
+             (const uint64_t*)w.keys, (const uint32_t*)w.cand_index, w.sc, w.hist);
+    LAUNCH("regupd_apply", s, grid, blk, k_regupd_apply, (uint64_t)n, f, e, kc, (const uint64_t*)w.ballots_ejected,
+           (const uint32_t*)w.offset_ejected, (const uint64_t*)w.sc, d_indices, (uint64_t*)d_values,
+           (unsigned long long*)d_summary);
+    return 0;
+  });
+}
+
+int bls381_registry_updates(size_t n, const uint8_t* activation_eligibility_epoch, const uint8_t* activation_epoch,
+                            const uint8_t* exit_epoch, const uint8_t* withdrawable_epoch, const uint8_t* effective_balance,
+                            size_t stride, uint64_t current_epoch, uint64_t finalized_epoch,
+                            const bls381_registry_constants* constants, uint32_t* indices, uint8_t* values,
+                            uint64_t summary[8]) {
+  return guarded([&]() -> int {
+    registry_constants kc;
+    regupd_epochs e;
+    if ((uint64_t)n > 0xFFFFFFFFull || !field_ok(n, stride) || !summary ||
+        !regupd_scalars_ok(n, constants, current_epoch, &finalized_epoch, &kc, &e))
+      return BLS381_EARG;
+    if (n && (!activation_eligibility_epoch || !activation_epoch || !exit_epoch || !withdrawable_epoch ||
+              !effective_balance || !indices || !values))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(activation_eligibility_epoch, stride);
+    hf.add(activation_epoch, stride);
+    hf.add(exit_epoch, stride);
+    hf.add(withdrawable_epoch, stride);
+    hf.add(effective_balance, stride);
+    hf.plan(n);
+    const size_t wsb = bls381_registry_updates_workspace_size(n);
+    uint64_t *d_val, *d_sum;
+    uint32_t* d_idx;
+    uint8_t* d_ws;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_val = b.take<uint64_t>(4 * n);
+      d_sum = b.take<uint64_t>(RS_WORDS);
+      d_idx = b.take<uint32_t>(n);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(bls381_registry_updates_device(n, hf.dev(0), hf.dev(1), hf.dev(2), hf.dev(3), hf.dev(4), stride, current_epoch,
+                                       finalized_epoch, constants, d_idx, (uint8_t*)d_val, d_sum, d_ws, hc.s));
+    uint64_t sum[RS_WORDS];
+    TRY(hc.download(sum, d_sum, 8 * RS_WORDS));
+    HIPC(hipStreamSynchronize(hc.s));   // the status decides whether anything comes back
+    if (sum[RS_STATUS] & REGUPD_STATUS_NO_CHURN) return BLS381_EARG;   // nothing was written
+    TRY(hc.download(indices, d_idx, 4 * n));
+    TRY(hc.download(values, d_val, 32 * n));
+    TRY(hc.finish());
+    for (uint32_t x = 0; x < RS_WORDS; ++x) summary[x] = sum[x];
+    return 0;
+  });
+}
+
 }  // extern "C"
 
 // ---- multi-GPU over RCCL: one process per GPU, a communicator

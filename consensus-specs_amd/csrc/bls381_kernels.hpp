@@ -18,6 +18,7 @@
 #include "bls381_shuffle.hpp"
 #include "bls381_epoch.hpp"
 #include "bls381_rewards.hpp"
+#include "bls381_regupd.hpp"
 #include "bls381_keytable.hpp"
 
 namespace bls381 {
@@ -2404,6 +2405,330 @@ __global__ void __launch_bounds__(EPOCH_BLOCK) k_effective_balances(uint64_t n, 
   if (threadIdx.x == 0) {
     const uint32_t c = wave_moved[0] + wave_moved[1] + wave_moved[2] + wave_moved[3];
     if (c) atomicAdd(changed, (unsigned long long)c);
+  }
+}
+
+// ------------------------------ registry updates: ejections, exit queue, activations (§7h) ----
+// (the facts, the queue's closed form and the composite's digits: bls381_regupd.hpp; the tile
+// geometry is the active indices')
+// Tile blockIdx.x: its ballots of `ejected` and `candidate`, its counts of active, ejected and
+// candidate validators (tile_count[3 tile ..]) and its exit peak.  queue_only: activation_epoch and
+// exit_epoch alone are read and no ballot is kept.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_regupd_count(uint64_t n, regupd_fields f, regupd_epochs e,
+                                                              registry_constants kc, int queue_only,
+                                                              uint64_t* __restrict__ ballots_ejected,
+                                                              uint64_t* __restrict__ ballots_candidate,
+                                                              uint32_t* __restrict__ tile_count,
+                                                              uint64_t* __restrict__ tile_peak_epoch,
+                                                              uint32_t* __restrict__ tile_peak_count) {
+  __shared__ uint32_t wave_count[3][EPOCH_BLOCK / 64];
+  __shared__ uint64_t lane_epoch[EPOCH_BLOCK];
+  __shared__ uint32_t lane_count[EPOCH_BLOCK];
+  const size_t tile = blockIdx.x;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  uint32_t active = 0, ejected = 0, candidate = 0;   // the same on every lane of a wave
+  exit_peak peak{0, 0};
+  for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k) {
+    const uint64_t i = active_item(tile, k, tid);
+    bool a = false, ej = false, cd = false;
+    if (i < n) {
+      if (queue_only) {   // the same for the whole launch
+        const uint64_t ext = field_load(f.exit_, (size_t)i);
+        a = field_load(f.activation, (size_t)i) <= e.cur && e.cur < ext;
+        peak = peak_combine(peak, peak_of(ext));
+      } else {
+        const regupd_item it = regupd_load(f, (size_t)i, e, kc);
+        a = it.active;
+        ej = it.ejected;
+        cd = it.candidate;
+        peak = peak_combine(peak, peak_of(it.ext));
+      }
+    }
+    const uint64_t ma = __ballot(a), me = __ballot(ej), mc = __ballot(cd);
+    if (!queue_only && (tid & 63u) == 0) {
+      ballots_ejected[tile * ACTIVE_TILE_BALLOTS + 4 * k + wave] = me;
+      ballots_candidate[tile * ACTIVE_TILE_BALLOTS + 4 * k + wave] = mc;
+    }
+    active += (uint32_t)__popcll(ma);
+    ejected += (uint32_t)__popcll(me);
+    candidate += (uint32_t)__popcll(mc);
+  }
+  if ((tid & 63u) == 0) {
+    wave_count[0][wave] = active;
+    wave_count[1][wave] = ejected;
+    wave_count[2][wave] = candidate;
+  }
+  lane_epoch[tid] = peak.epoch;
+  lane_count[tid] = peak.count;
+  for (uint32_t s = EPOCH_BLOCK / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (tid < s) {
+      const exit_peak p = peak_combine(exit_peak{lane_epoch[tid], lane_count[tid]},
+                                       exit_peak{lane_epoch[tid + s], lane_count[tid + s]});
+      lane_epoch[tid] = p.epoch;
+      lane_count[tid] = p.count;
+    }
+  }
+  __syncthreads();
+  if (tid < 3) tile_count[3 * tile + tid] = wave_count[tid][0] + wave_count[tid][1] + wave_count[tid][2] + wave_count[tid][3];
+  if (tid == 0) {
+    tile_peak_epoch[tile] = lane_epoch[0];
+    tile_peak_count[tile] = lane_count[0];
+  }
+}
+
+// One workgroup: the exclusive scans of the tiles' ejected and candidate counts, 256 tiles a round,
+// the active count, the registry's exit peak, and from them the call's scalars (sc: RU_*).
+// summary (RS_*, zeroed before) and queue_out (E0, c0, L, active count) may be NULL.  tiles == 0
+// writes the scalars of an empty registry.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_regupd_scan(size_t tiles, const uint32_t* __restrict__ tile_count,
+                                                             const uint64_t* __restrict__ tile_peak_epoch,
+                                                             const uint32_t* __restrict__ tile_peak_count,
+                                                             uint32_t* __restrict__ tile_offset_ejected,
+                                                             uint32_t* __restrict__ tile_offset_candidate,
+                                                             registry_constants kc, uint64_t delayed_cur,
+                                                             uint64_t* __restrict__ sc, uint64_t* __restrict__ summary,
+                                                             uint64_t* __restrict__ queue_out) {
+  __shared__ uint32_t scan_e[EPOCH_BLOCK];
+  __shared__ uint32_t scan_c[EPOCH_BLOCK];
+  __shared__ uint64_t lane_epoch[EPOCH_BLOCK];
+  __shared__ uint64_t lane_active[EPOCH_BLOCK];
+  __shared__ uint32_t lane_count[EPOCH_BLOCK];
+  const uint32_t tid = threadIdx.x;
+  const size_t rounds = (tiles + EPOCH_BLOCK - 1) / EPOCH_BLOCK;
+  uint64_t carry_e = 0, carry_c = 0, active = 0;
+  exit_peak peak{0, 0};
+  for (size_t r = 0; r < rounds; ++r) {
+    const size_t j = r * EPOCH_BLOCK + tid;
+    uint32_t ce = 0, cc = 0;
+    if (j < tiles) {
+      active += tile_count[3 * j];
+      ce = tile_count[3 * j + 1];
+      cc = tile_count[3 * j + 2];
+      peak = peak_combine(peak, exit_peak{tile_peak_epoch[j], tile_peak_count[j]});
+    }
+    scan_e[tid] = ce;
+    scan_c[tid] = cc;
+    __syncthreads();
+    for (uint32_t d = 1; d < EPOCH_BLOCK; d <<= 1) {   // inclusive scans in place
+      const uint32_t ve = tid >= d ? scan_e[tid - d] : 0, vc = tid >= d ? scan_c[tid - d] : 0;
+      __syncthreads();
+      scan_e[tid] += ve;
+      scan_c[tid] += vc;
+      __syncthreads();
+    }
+    if (j < tiles) {
+      tile_offset_ejected[j] = (uint32_t)(carry_e + scan_e[tid] - ce);
+      tile_offset_candidate[j] = (uint32_t)(carry_c + scan_c[tid] - cc);
+    }
+    carry_e += scan_e[EPOCH_BLOCK - 1];
+    carry_c += scan_c[EPOCH_BLOCK - 1];
+    __syncthreads();   // the scans are rewritten next round
+  }
+  lane_active[tid] = active;
+  lane_epoch[tid] = peak.epoch;
+  lane_count[tid] = peak.count;
+  for (uint32_t s = EPOCH_BLOCK / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (tid < s) {
+      const exit_peak p = peak_combine(exit_peak{lane_epoch[tid], lane_count[tid]},
+                                       exit_peak{lane_epoch[tid + s], lane_count[tid + s]});
+      lane_epoch[tid] = p.epoch;
+      lane_count[tid] = p.count;
+      lane_active[tid] += lane_active[tid + s];
+    }
+  }
+  if (tid == 0) {
+    const regupd_queue q = regupd_derive(lane_active[0], exit_peak{lane_epoch[0], lane_count[0]}, delayed_cur, kc);
+    sc[RU_L] = q.L;
+    sc[RU_E0] = q.E0;
+    sc[RU_C0] = q.c0;
+    sc[RU_K] = carry_c;
+    sc[RU_TKEY] = ~(uint64_t)0;   // at most L candidates: everyone is at or below it
+    sc[RU_TIDX] = ~(uint64_t)0;
+    sc[RU_ACTIVE] = lane_active[0];
+    sc[RU_EJECTED] = carry_e;
+    sc[RU_SEL] = 0;
+    sc[RU_SEL + 1] = 0;
+    sc[RU_SEL + 2] = q.L - 1;     // the L-th smallest has L - 1 before it
+    if (summary) {
+      summary[RS_EJECTED] = q.L ? carry_e : 0;
+      summary[RS_ACTIVE] = lane_active[0];
+      summary[RS_CHURN] = q.L;
+      summary[RS_E0] = q.E0;
+      if (q.L == 0) summary[RS_STATUS] = REGUPD_STATUS_NO_CHURN;
+    }
+    if (queue_out) {
+      queue_out[0] = q.E0;
+      queue_out[1] = q.c0;
+      queue_out[2] = q.L;
+      queue_out[3] = lane_active[0];
+    }
+  }
+}
+
+// Tile blockIdx.x: its candidates to the dense list (key = elig', index), in index order
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_regupd_compact(const uint64_t* __restrict__ ballots,
+                                                                const uint32_t* __restrict__ tile_offset,
+                                                                u64_field eligibility, u64_field effective,
+                                                                uint64_t cur, uint64_t max_effective_balance,
+                                                                uint64_t* __restrict__ keys,
+                                                                uint32_t* __restrict__ indices) {
+  __shared__ uint32_t before[ACTIVE_TILE_BALLOTS];
+  const size_t tile = blockIdx.x;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  const uint64_t* mine = ballots + tile * ACTIVE_TILE_BALLOTS;
+  if (tid == 0) {
+    uint32_t at = 0;
+    for (uint32_t b = 0; b < ACTIVE_TILE_BALLOTS; ++b) {
+      before[b] = at;
+      at += (uint32_t)__popcll(mine[b]);
+    }
+  }
+  __syncthreads();
+  const uint32_t base = tile_offset[tile];
+  for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k) {
+    const uint64_t m = mine[4 * k + wave];
+    if ((m >> (tid & 63u)) & 1u) {
+      // a set bit is a validator below n (k_regupd_count), and its position is below K <= n
+      const uint32_t lanes_before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      const uint64_t i = active_item(tile, k, tid);
+      const uint64_t el = field_load(eligibility, (size_t)i);
+      const size_t at = (size_t)base + before[4 * k + wave] + lanes_before;
+      keys[at] = (el == FAR_FUTURE && field_load(effective, (size_t)i) >= max_effective_balance) ? cur : el;
+      indices[at] = (uint32_t)i;
+    }
+  }
+}
+
+// Radix select, launch `pass` of 0 .. 12.  Every workgroup fixes digit pass - 1 from the histogram
+// the launch before completed (workgroup 0 records the prefix and the rank left as entry `pass` of
+// sc[RU_SEL ..], which this launch does not read); then it adds the digit-`pass` histogram of its
+// 2,048 entries that carry the prefix to hist[256 pass ..].  Launch 12 only fixes the last digit
+// and writes the threshold.  With K <= L nothing runs and the threshold stays at all-ones.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_regupd_select(uint32_t pass, const uint64_t* __restrict__ keys,
+                                                               const uint32_t* __restrict__ indices, uint64_t* sc,
+                                                               uint32_t* hist) {
+  __shared__ uint32_t bins[REGUPD_BINS];
+  __shared__ uint32_t scan[REGUPD_BINS];
+  __shared__ uint64_t fixed[3];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t K = sc[RU_K], L = sc[RU_L];
+  if (K <= L || L == 0) return;   // the same for the whole launch
+  const uint64_t first = (uint64_t)blockIdx.x * ACTIVE_TILE;
+  if (first >= K && blockIdx.x != 0) return;
+  uint64_t pkey = 0, rank = L - 1;
+  uint32_t pidx = 0;
+  if (pass > 0) {
+    pkey = sc[RU_SEL + 3 * (pass - 1)];
+    pidx = (uint32_t)sc[RU_SEL + 3 * (pass - 1) + 1];
+    rank = sc[RU_SEL + 3 * (pass - 1) + 2];
+    const uint32_t c = hist[REGUPD_BINS * (pass - 1) + tid];
+    scan[tid] = c;
+    __syncthreads();
+    for (uint32_t d = 1; d < REGUPD_BINS; d <<= 1) {
+      const uint32_t v = tid >= d ? scan[tid - d] : 0;
+      __syncthreads();
+      scan[tid] += v;
+      __syncthreads();
+    }
+    const uint64_t incl = scan[tid], excl = incl - c;
+    if (excl <= rank && rank < incl) {   // one bin: the bins sum to more than rank
+      regupd_prefix_push(&pkey, &pidx, pass - 1, tid);
+      fixed[0] = pkey;
+      fixed[1] = pidx;
+      fixed[2] = rank - excl;
+    }
+    __syncthreads();
+    pkey = fixed[0];
+    pidx = (uint32_t)fixed[1];
+    rank = fixed[2];
+    if (blockIdx.x == 0 && tid == 0) {
+      sc[RU_SEL + 3 * pass] = pkey;
+      sc[RU_SEL + 3 * pass + 1] = pidx;
+      sc[RU_SEL + 3 * pass + 2] = rank;
+      if (pass == REGUPD_DIGITS) {
+        sc[RU_TKEY] = pkey;
+        sc[RU_TIDX] = pidx;
+      }
+    }
+  }
+  if (pass == REGUPD_DIGITS) return;
+  bins[tid] = 0;
+  __syncthreads();
+  for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k) {
+    const uint64_t j = first + (uint64_t)k * EPOCH_BLOCK + tid;
+    if (j < K) {
+      const uint64_t key = keys[j];
+      const uint32_t idx = indices[j];
+      if (regupd_prefix_match(key, idx, pkey, pidx, pass)) atomicAdd(&bins[regupd_digit(key, idx, pass)], 1u);
+    }
+  }
+  __syncthreads();
+  if (bins[tid]) atomicAdd(&hist[REGUPD_BINS * pass + tid], bins[tid]);
+}
+
+// Tile blockIdx.x, one lane per validator and round: indices[i] = i and values[4 i ..] = the four
+// epochs where any of them changes, 0xFFFFFFFF and the old epochs where none does.  The ejection
+// rank is the tile's offset plus the ballots before; the activation is the lane's own comparison
+// with the threshold.  One atomic add per workgroup and counter into summary.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_regupd_apply(uint64_t n, regupd_fields f, regupd_epochs e,
+                                                              registry_constants kc,
+                                                              const uint64_t* __restrict__ ballots_ejected,
+                                                              const uint32_t* __restrict__ tile_offset_ejected,
+                                                              const uint64_t* __restrict__ sc,
+                                                              uint32_t* __restrict__ indices,
+                                                              uint64_t* __restrict__ values,
+                                                              unsigned long long* summary) {
+  __shared__ uint32_t before[ACTIVE_TILE_BALLOTS];
+  __shared__ uint32_t wave_count[4][EPOCH_BLOCK / 64];
+  const size_t tile = blockIdx.x;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  const uint64_t* mine = ballots_ejected + tile * ACTIVE_TILE_BALLOTS;
+  if (tid == 0) {
+    uint32_t at = 0;
+    for (uint32_t b = 0; b < ACTIVE_TILE_BALLOTS; ++b) {
+      before[b] = at;
+      at += (uint32_t)__popcll(mine[b]);
+    }
+  }
+  __syncthreads();
+  const regupd_queue q{sc[RU_L], sc[RU_E0], sc[RU_C0]};
+  const uint64_t tkey = sc[RU_TKEY], tidx = sc[RU_TIDX];
+  const uint64_t base = tile_offset_ejected[tile];
+  uint32_t eligible = 0, activated = 0, changed = 0, wrapped = 0;   // the same on every lane of a wave
+  for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k) {
+    const uint64_t i = active_item(tile, k, tid);
+    regupd_result r;
+    r.changed = r.eligible_set = r.activated = r.wrapped = false;
+    if (i < n) {
+      regupd_item it = regupd_load(f, (size_t)i, e, kc);
+      if (q.L == 0) {   // no churn limit: nothing moves (the status word says so)
+        it.new_elig = it.elig;
+        it.ejected = it.candidate = false;
+      }
+      const uint64_t m = mine[4 * k + wave];
+      const uint32_t lanes_before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      r = regupd_apply_item(it, (uint32_t)i, base + before[4 * k + wave] + lanes_before, q, tkey, tidx, e, kc);
+      indices[i] = r.changed ? (uint32_t)i : REGUPD_NONE;
+      for (int x = 0; x < 4; ++x) values[4 * i + x] = r.v[x];
+    }
+    eligible += (uint32_t)__popcll(__ballot(r.eligible_set));
+    activated += (uint32_t)__popcll(__ballot(r.activated));
+    changed += (uint32_t)__popcll(__ballot(r.changed));
+    wrapped += (uint32_t)__popcll(__ballot(r.wrapped));
+  }
+  if ((tid & 63u) == 0) {
+    wave_count[0][wave] = eligible;
+    wave_count[1][wave] = activated;
+    wave_count[2][wave] = changed;
+    wave_count[3][wave] = wrapped;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    const uint32_t c = wave_count[tid][0] + wave_count[tid][1] + wave_count[tid][2] + wave_count[tid][3];
+    const uint32_t at = tid == 0 ? RS_ELIGIBLE : tid == 1 ? RS_ACTIVATED : tid == 2 ? RS_CHANGED : RS_STATUS;
+    if (c) atomicAdd(summary + at, (unsigned long long)c);
   }
 }
 

@@ -1543,3 +1543,6 @@ long hc_scope_scenario(const char* name, int fail_at, char* out, size_t cap) {
 // ---- epoch rewards (bls381_rewards.hpp): hc_mul_div_u64, hc_isqrt_u64, hc_epoch_votes,
 // hc_epoch_deltas, hc_epoch_slashings, hc_effective_balances
 #include "host_check_rewards.hpp"
+
+// ---- registry updates (bls381_regupd.hpp): hc_exit_queue, hc_registry_updates
+#include "host_check_regupd.hpp"

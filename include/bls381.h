@@ -885,6 +885,81 @@ int bls381_effective_balances_device(size_t n, const uint64_t* d_balances, const
                                      size_t stride, uint64_t increment, uint64_t max_effective_balance,
                                      uint32_t* d_indices, uint64_t* d_values, uint64_t* d_changed, void* stream);
 
+/* ---- registry updates: ejections, the exit queue and the activation queue --- */
+/* process_registry_updates (0_beacon-chain.md:1480-1502) with initiate_validator_exit (:1110-1128)
+ * and get_churn_limit (:1081-1088) over the records where they are.  Validator
+ * fields are little-endian uint64 at base + i * stride as above, one `stride` for the five fields of
+ * a call: 121 with bases records + 80 / 88 / 96 / 104 / 113 for activation_eligibility_epoch /
+ * activation_epoch / exit_epoch / withdrawable_epoch / effective_balance, or 8 over plain arrays.
+ * With FAR = 2^64 - 1, cur = current_epoch and delayed(e) = e + 1 + activation_exit_delay:
+ *   eligibility   activation_eligibility_epoch becomes cur where it is FAR and effective_balance >=
+ *                 max_effective_balance.
+ *   ejections     a validator active at cur (activation_epoch <= cur < exit_epoch) with
+ *                 effective_balance <= ejection_balance and exit_epoch == FAR leaves through the exit
+ *                 queue: with L = max(min_per_epoch_churn_limit, active count /
+ *                 churn_limit_quotient), E0 = the largest exit_epoch != FAR in the registry or
+ *                 delayed(cur), whichever is larger, and c0 = how many validators hold E0, the k-th
+ *                 ejected validator in index order (k from 0) gets exit_epoch = E0 + (min(c0, L) + k)
+ *                 / L and withdrawable_epoch = exit_epoch + min_validator_withdrawability_delay.
+ *   activations   the candidates (eligibility != FAR after the first step, activation_epoch >=
+ *                 delayed(finalized_epoch)) in the order of (eligibility, index); the first L of
+ *                 them are dequeued, and a dequeued one whose activation_epoch is FAR gets
+ *                 delayed(cur).  One that already has an activation epoch takes a place and keeps it.
+ * These are the spec's loops in closed form; every result is the spec's integer.
+ *
+ * bls381_registry_updates: indices[i] = i where any of validator i's four epochs changes and
+ * 0xFFFFFFFF where none does; values[32 i ..] = activation_eligibility_epoch, activation_epoch,
+ * exit_epoch, withdrawable_epoch, new or old, as four little-endian uint64.
+ * bls381_list_tree_update_device takes the two arrays as they are (off = 80, len = 32, n_upd = n).
+ * summary: [0] eligibilities set, [1] validators ejected, [2] validators activated, [3] validators
+ * changed, [4] the active count at cur, [5] L, [6] E0 before the call, [7] the status word.  An
+ * exit_epoch or withdrawable_epoch that would pass 2^64 - 1 becomes 2^64 - 1 and its validator adds
+ * 1 to the status word.  n == 0 writes the summary alone (E0 = delayed(cur), L = the minimum).
+ *
+ * bls381_exit_queue: initiate_validator_exit's view of the registry (:1119-1124): queue[0] = E0,
+ * [1] = c0, [2] = L, [3] = the active count.  The next exit gets E0 + (min(c0, L) + k) / L with k
+ * the exits the caller has made since, so a block's voluntary exits and slashings are arithmetic.
+ * The device form has no status word: where the data gives no churn limit (see below) it writes
+ * queue[2] = 0 and returns BLS381_OK, so its caller checks queue[2] before dividing by it.
+ *
+ * BLS381_EARG: n above 2^32 - 1; a stride below 8; a NULL argument that is needed (fields, indices
+ * and values when n is not 0; constants, summary / d_summary, queue / d_queue and the workspace
+ * always); d_indices not 4-byte or d_values, d_summary, d_queue not 8-byte aligned;
+ * churn_limit_quotient of 0; current_epoch + 1 + activation_exit_delay or finalized_epoch + 1 +
+ * activation_exit_delay at or above 2^64; min_per_epoch_churn_limit of 0 with n <
+ * churn_limit_quotient.  A churn limit of 0 that only the data shows (min_per_epoch_churn_limit of 0
+ * and fewer than churn_limit_quotient active validators) is BLS381_EARG in the host forms, which
+ * then write nothing; the device forms cannot know: they report no change for every validator, L =
+ * 0, and bit 63 of the status word set.  Host-pointer forms stage, run on the engine's stream and
+ * return synchronised; device forms are queued on `stream`, never synchronise and read nothing
+ * back.  The workspace holds bls381_registry_updates_workspace_size(n) bytes (both calls; never 0
+ * for n up to 2^32 - 1). */
+typedef struct bls381_registry_constants {
+  uint64_t max_effective_balance;
+  uint64_t ejection_balance;
+  uint64_t activation_exit_delay;
+  uint64_t min_validator_withdrawability_delay;
+  uint64_t min_per_epoch_churn_limit;
+  uint64_t churn_limit_quotient;
+} bls381_registry_constants;
+size_t bls381_registry_updates_workspace_size(size_t n);
+int bls381_registry_updates(size_t n, const uint8_t* activation_eligibility_epoch, const uint8_t* activation_epoch,
+                            const uint8_t* exit_epoch, const uint8_t* withdrawable_epoch, const uint8_t* effective_balance,
+                            size_t stride, uint64_t current_epoch, uint64_t finalized_epoch,
+                            const bls381_registry_constants* constants, uint32_t* indices, uint8_t* values,
+                            uint64_t summary[8]);
+int bls381_registry_updates_device(size_t n, const uint8_t* d_activation_eligibility_epoch,
+                                   const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch,
+                                   const uint8_t* d_withdrawable_epoch, const uint8_t* d_effective_balance, size_t stride,
+                                   uint64_t current_epoch, uint64_t finalized_epoch,
+                                   const bls381_registry_constants* constants, uint32_t* d_indices, uint8_t* d_values,
+                                   uint64_t* d_summary, void* d_workspace, void* stream);
+int bls381_exit_queue(size_t n, const uint8_t* activation_epoch, const uint8_t* exit_epoch, size_t stride,
+                      uint64_t current_epoch, const bls381_registry_constants* constants, uint64_t queue[4]);
+int bls381_exit_queue_device(size_t n, const uint8_t* d_activation_epoch, const uint8_t* d_exit_epoch, size_t stride,
+                             uint64_t current_epoch, const bls381_registry_constants* constants, uint64_t* d_queue,
+                             void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
