@@ -119,6 +119,15 @@ _SIGS = {
                                             ctypes.c_int, _u8p]),
     "bls381_ssz_list_root_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_size_t, ctypes.c_size_t, _u8p,
                                                    ctypes.c_uint32, ctypes.c_int, _u8p, _u8p, _u8p]),
+    "bls381_ssz_ragged_roots_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_ssz_ragged_roots": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p]),
+    "bls381_ssz_ragged_roots_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_size_t, _u8p, _u8p,
+                                                      ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_ssz_ragged_list_root_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_ssz_ragged_list_root": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_int,
+                                                   _u8p, _u8p]),
+    "bls381_ssz_ragged_list_root_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_size_t, _u8p, _u8p,
+                                                          ctypes.c_uint32, ctypes.c_int, _u8p, _u8p, _u8p, _u8p]),
     "bls381_deposits_build_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
     "bls381_deposits_build": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, _u8p, _u8p]),
     "bls381_deposits_build_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),

@@ -22,6 +22,13 @@ utils/merkle_minimal.py trees (zero-padded to 2**depth leaves, the given ones fr
 ``first``), ``build_deposits`` turns DepositData into Deposits with their proofs under one
 root.  ``hash_tree_root(typ, value)`` and ``signing_root(typ, value)`` take Python values of any
 type below, ``List(elem)`` and ``BYTES`` (the spec's ``bytes``) included.
+
+Variable-size containers (csrc/bls381_ssz.hpp ``ssz_run_ragged``): a container whose
+variable-size fields are lists of basic elements or such containers again -- ``PendingAttestation``,
+``Attestation``, ``IndexedAttestation``, ``AttesterSlashing`` -- compiles into a ragged program that
+follows the offsets of its serialization, so ``hash_tree_root_ragged_batch`` and ``list_root_ragged``
+take a whole batch of them in one call, and ``hash_tree_root`` of a list of them is one call too.
+Serialized items are untrusted: one that breaks the offset rules gets status 1 and a zero root.
 """
 from __future__ import annotations
 
@@ -33,6 +40,15 @@ from . import _native
 
 SSZ_CHUNK = 1
 SSZ_MERKLE = 2
+# the ops of a ragged program (csrc/bls381_defs.hpp)
+SSZ_RAGGED = 3
+SSZ_FIELD = 4
+SSZ_ENTER = 5
+SSZ_LEAVE = 6
+SSZ_NO_NEXT = 0xFFFFFFFF
+SSZ_SCOPE_MAX = 4
+SSZ_FIXED_MAX = 1 << 16
+BYTES_PER_LENGTH_OFFSET = 4
 
 
 def uint(n: int):
@@ -87,6 +103,22 @@ VoluntaryExit = Container(("epoch", uint(8)), ("validator_index", uint(8)), ("si
 Transfer = Container(("sender", uint(8)), ("recipient", uint(8)), ("amount", uint(8)), ("fee", uint(8)),
                      ("slot", uint(8)), ("pubkey", Bytes(48)), ("signature", Bytes(96)))
 
+# the variable-size containers of 0_beacon-chain.md:345-523 and the block around them
+IndexedAttestation = Container(("custody_bit_0_indices", List(uint(8))), ("custody_bit_1_indices", List(uint(8))),
+                               ("data", AttestationData), ("signature", Bytes(96)))
+PendingAttestation = Container(("aggregation_bitfield", BYTES), ("data", AttestationData),
+                               ("inclusion_delay", uint(8)), ("proposer_index", uint(8)))
+AttesterSlashing = Container(("attestation_1", IndexedAttestation), ("attestation_2", IndexedAttestation))
+Attestation = Container(("aggregation_bitfield", BYTES), ("data", AttestationData), ("custody_bitfield", BYTES),
+                        ("signature", Bytes(96)))
+BeaconBlockBody = Container(("randao_reveal", Bytes(96)), ("eth1_data", Eth1Data), ("graffiti", Bytes(32)),
+                            ("proposer_slashings", List(ProposerSlashing)),
+                            ("attester_slashings", List(AttesterSlashing)), ("attestations", List(Attestation)),
+                            ("deposits", List(Deposit)), ("voluntary_exits", List(VoluntaryExit)),
+                            ("transfers", List(Transfer)))
+BeaconBlock = Container(("slot", uint(8)), ("parent_root", Bytes(32)), ("state_root", Bytes(32)),
+                        ("body", BeaconBlockBody), ("signature", Bytes(96)))
+
 
 def is_fixed_size(typ) -> bool:
     """ssz_impl.py:43-53."""
@@ -113,8 +145,26 @@ def item_size(typ) -> int:
     return sum(item_size(t) for _, t in typ[1])
 
 
+def _encode_series(types, values) -> bytes:
+    """ssz_impl.py:72-103: the fixed parts in order, a 4-byte offset in place of each variable-size
+    part, then the variable parts."""
+    parts = [(is_fixed_size(t), serialize(t, x)) for t, x in zip(types, values)]
+    offset = sum(len(p) if fixed else BYTES_PER_LENGTH_OFFSET for fixed, p in parts)
+    if offset + sum(len(p) for fixed, p in parts if not fixed) >= 1 << (8 * BYTES_PER_LENGTH_OFFSET):
+        raise ValueError("the serialization does not fit 32-bit offsets")
+    head, tail = [], []
+    for fixed, p in parts:
+        if fixed:
+            head.append(p)
+        else:
+            head.append(offset.to_bytes(BYTES_PER_LENGTH_OFFSET, "little"))
+            tail.append(p)
+            offset += len(p)
+    return b"".join(head + tail)
+
+
 def serialize(typ, v) -> bytes:
-    """SSZ serialization of a fixed-size value (ssz_impl.py:21-30 for basics; fields concatenated)."""
+    """SSZ serialization (ssz_impl.py:21-30 for basics, :60-103 for series and containers)."""
     k = typ[0]
     if k == "uint":
         return int(v).to_bytes(typ[1], "little")
@@ -125,12 +175,13 @@ def serialize(typ, v) -> bytes:
         if len(v) != typ[1]:
             raise ValueError("expected %d bytes" % typ[1])
         return v
-    if k == "vector":
-        v = list(v)
-        if len(v) != typ[2]:
+    if k in ("vector", "list"):
+        if k == "vector" and len(v) != typ[2]:
             raise ValueError("expected %d elements" % typ[2])
-        return b"".join(serialize(typ[1], x) for x in v)
-    return b"".join(serialize(t, v[name]) for name, t in typ[1])
+        if isinstance(v, (bytes, bytearray)) and typ[1] == uint(1):
+            return bytes(v)
+        return _encode_series([typ[1]] * len(v), list(v))
+    return _encode_series([t for _, t in typ[1]], [v[name] for name, _ in typ[1]])
 
 
 def _emit(typ, off: int, prog: list) -> int:
@@ -161,12 +212,48 @@ def _emit(typ, off: int, prog: list) -> int:
     return off
 
 
+def fixed_part_size(typ) -> int:
+    """Bytes of a container's fixed part: its fixed-size fields and an offset word per variable one."""
+    return sum(item_size(t) if is_fixed_size(t) else BYTES_PER_LENGTH_OFFSET for _, t in typ[1])
+
+
+def _emit_scope(typ, count: int, prog: list) -> None:
+    """The ops over one scope of a ragged program: the first `count` fields of the container."""
+    pos, off = [], 0
+    for _, t in typ[1]:
+        pos.append(off)
+        off += item_size(t) if is_fixed_size(t) else BYTES_PER_LENGTH_OFFSET
+    var = [i for i, (_, t) in enumerate(typ[1]) if not is_fixed_size(t)]
+    for i, (_, t) in enumerate(typ[1][:count]):
+        if is_fixed_size(t):
+            _emit(t, pos[i], prog)
+            continue
+        later = [pos[j] for j in var if j > i]
+        nxt = later[0] if later else SSZ_NO_NEXT
+        if t[0] == "list" and t[1][0] in ("uint", "bool"):
+            prog += [SSZ_FIELD, pos[i], nxt, item_size(t[1])]
+        elif t[0] == "container":
+            prog += [SSZ_ENTER, pos[i], nxt, fixed_part_size(t)]
+            _emit_scope(t, len(t[1]), prog)
+            prog += [SSZ_LEAVE]
+        else:
+            raise ValueError("a ragged program takes lists of basic elements and containers of them")
+    prog += [SSZ_MERKLE, count]
+
+
 def compile_root(typ, signing: bool = False) -> np.ndarray:
-    """The root program of `typ` (signing=True: signing_root, the last field left out)."""
+    """The root program of `typ` (signing=True: signing_root, the last field left out).  A
+    variable-size container gives a ragged program; ValueError when a variable-size field of it
+    is neither a list of basic elements nor such a container."""
     prog: list = []
-    if signing:
-        if typ[0] != "container" or len(typ[1]) < 2:
-            raise ValueError("signing_root needs a container with at least two fields")
+    if signing and (typ[0] != "container" or len(typ[1]) < 2):
+        raise ValueError("signing_root needs a container with at least two fields")
+    if typ[0] == "container" and not is_fixed_size(typ):
+        prog += [SSZ_RAGGED, fixed_part_size(typ)]
+        _emit_scope(typ, len(typ[1]) - (1 if signing else 0), prog)
+    elif not is_fixed_size(typ):
+        raise ValueError("a root program takes a fixed-size type or a variable-size container")
+    elif signing:
         off = 0
         for _, t in typ[1][:-1]:
             off = _emit(t, off, prog)
@@ -200,6 +287,101 @@ def hash_tree_root_batch(typ, serialized_items) -> list:
 def signing_root_batch(typ, serialized_items) -> list:
     """signing_root of each serialized container (ssz_impl.py:158-163)."""
     return _roots(typ, serialized_items, True)
+
+
+def ragged_prog_ok(prog, max_field_bytes: int = 0) -> bool:
+    """csrc/bls381_plan.hpp ssz_ragged_prog_ok: the walk the engine makes before it runs a ragged
+    program (max_field_bytes 0: the longest field a 32-bit offset admits)."""
+    prog = [int(x) for x in prog]
+    n = len(prog)
+    if n < 2 or n > SSZ_PROG_MAX or prog[0] != SSZ_RAGGED or prog[1] > SSZ_FIXED_MAX:
+        return False
+    if max_field_bytes <= 0 or max_field_bytes > 0xFFFFFFFF:
+        max_field_bytes = 0xFFFFFFFF
+    stream = chunk_depth((max_field_bytes + 31) // 32) + 1
+    fixed, sp, peak, pc = [prog[1]], 0, 0, 2
+    while pc < n:
+        op = prog[pc]
+        if op == SSZ_CHUNK and pc + 2 < n:
+            if prog[pc + 2] > 32 or prog[pc + 1] + prog[pc + 2] > fixed[-1]:
+                return False
+            sp, pc = sp + 1, pc + 3
+        elif op == SSZ_MERKLE and pc + 1 < n:
+            k = prog[pc + 1]
+            if k == 0 or k > sp:
+                return False
+            peak = max(peak, sp - k + (1 << chunk_depth(k)))
+            sp, pc = sp - k + 1, pc + 2
+        elif op in (SSZ_FIELD, SSZ_ENTER) and pc + 3 < n:
+            pos, nxt, arg = prog[pc + 1:pc + 4]
+            if pos + 4 > fixed[-1] or (nxt != SSZ_NO_NEXT and nxt + 4 > fixed[-1]):
+                return False
+            if op == SSZ_FIELD:
+                if arg not in (1, 2, 4, 8, 16, 32):
+                    return False
+                peak = max(peak, sp + stream)
+                sp += 1
+            else:
+                if len(fixed) >= SSZ_SCOPE_MAX or arg > SSZ_FIXED_MAX:
+                    return False
+                fixed.append(arg)
+            pc += 4
+        elif op == SSZ_LEAVE:
+            if len(fixed) == 1:
+                return False
+            fixed.pop()
+            pc += 1
+        else:
+            return False
+        peak = max(peak, sp)
+    return sp == 1 and len(fixed) == 1 and peak <= SSZ_STACK
+
+
+def _ragged_fits(typ) -> bool:
+    """Whether `typ` is a variable-size container that one lane roots from its serialization."""
+    if typ[0] != "container" or is_fixed_size(typ):
+        return False
+    try:
+        return ragged_prog_ok(compile_root(typ))
+    except ValueError:
+        return False
+
+
+def _ragged_args(typ, serialized_items):
+    items = [bytes(x) for x in serialized_items]
+    prog = compile_root(typ)
+    if is_fixed_size(typ) or not ragged_prog_ok(prog):
+        raise ValueError("not a type with a ragged root program")
+    starts = np.zeros(len(items) + 1, dtype=np.uint64)
+    np.cumsum([len(x) for x in items], out=starts[1:])
+    return items, b"".join(items), starts, prog
+
+
+def hash_tree_root_ragged_batch(typ, serialized_items):
+    """(roots, status): hash_tree_root of each serialized variable-size container, in one call.  A
+    serialization that breaks the offset rules has status 1 and a zero root."""
+    items, blob, starts, prog = _ragged_args(typ, serialized_items)
+    n = len(items)
+    status = np.zeros(n, dtype=np.uint8)
+    if n == 0:
+        return [], status
+    out = ctypes.create_string_buffer(32 * n)
+    _native.check(_native.lib().bls381_ssz_ragged_roots(n, blob or None, starts.ctypes.data_as(ctypes.c_void_p),
+                                                        prog.ctypes.data_as(ctypes.c_void_p), len(prog), out,
+                                                        status.ctypes.data_as(ctypes.c_void_p)))
+    raw = out.raw
+    return [raw[32 * i:32 * i + 32] for i in range(n)], status
+
+
+def list_root_ragged(typ, serialized_items, mix_length: bool = True) -> bytes:
+    """hash_tree_root of the list of the serialized variable-size containers, in one call;
+    ValueError when one of them breaks the offset rules."""
+    items, blob, starts, prog = _ragged_args(typ, serialized_items)
+    out = ctypes.create_string_buffer(32)
+    _native.check(_native.lib().bls381_ssz_ragged_list_root(
+        len(items), blob or None, starts.ctypes.data_as(ctypes.c_void_p), prog.ctypes.data_as(ctypes.c_void_p),
+        len(prog), int(bool(mix_length)), out, None))
+    return out.raw
 
 
 def verify_deposits(deposit_datas, domain) -> np.ndarray:
@@ -360,7 +542,10 @@ def _series_root(typ, v) -> bytes:
         _native.check(_native.lib().bls381_ssz_list_root(n, blob or None, size, prog.ctypes.data_as(ctypes.c_void_p),
                                                          len(prog), 1 if is_list else 0, out))
         return out.raw
-    # the slow path: variable-size elements (or ones too large for one lane), a call per element
+    if _ragged_fits(elem):
+        # variable-size containers of basic lists: the same, the roots following each item's offsets
+        return list_root_ragged(elem, [serialize(elem, x) for x in v], is_list)
+    # the slow path: other variable-size elements (or ones too large for one lane), a call per element
     roots = [hash_tree_root(elem, x) for x in v]
     return merkle_root(roots, chunk_depth(n), 0, n if is_list else None)
 
@@ -369,11 +554,14 @@ def hash_tree_root(typ, value) -> bytes:
     """hash_tree_root of a Python value (ssz_impl.py:143-155).  A fixed-size type that fits one
     lane's 64-chunk stack is one root program; a list or vector goes by its element -- fixed-size
     composite: one bls381_ssz_list_root call; basic, and ``bytes``: one bls381_merkle_root over the
-    zero-padded serialization; variable-size: a root per element, then their tree (the slow path:
-    one call per element) -- and a container with such fields combines its field roots through
-    merkle_root."""
+    zero-padded serialization; variable-size containers of basic lists: one
+    bls381_ssz_ragged_list_root call; other variable-size elements: a root per element, then their
+    tree (the slow path: one call per element) -- and a container with such fields combines its
+    field roots through merkle_root, unless it has a ragged program of its own."""
     if _program_fits(typ):
         return hash_tree_root_batch(typ, [serialize(typ, value)])[0]
+    if _ragged_fits(typ):
+        return hash_tree_root_ragged_batch(typ, [serialize(typ, value)])[0][0]
     if typ[0] in ("list", "vector"):
         return _series_root(typ, value)
     if typ[0] == "bytes":      # a BytesN of more than 64 chunks

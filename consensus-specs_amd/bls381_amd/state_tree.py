@@ -157,6 +157,95 @@ class ListTree:
         return [raw[self.item_size * i:self.item_size * (i + 1)] for i in range(n)]
 
 
+class RaggedListTree:
+    """A list of variable-size containers kept on the device: ``state.previous_epoch_attestations``
+    and ``state.current_epoch_attestations`` (List[PendingAttestation]).  It is a
+    ``ListTree(capacity, ssz.Bytes(32))`` over the elements' roots: a list of composites and the
+    list of their 32-byte roots have the same tree and the same length mix-in, so ``root()`` is the
+    list's ``hash_tree_root``.  ``append`` roots the serialized items on the device
+    (``bls381_ssz_ragged_roots_device``) and hands the roots, still in device memory, to
+    ``bls381_list_tree_append_device``.  Scratch buffers are torch tensors on the current device."""
+
+    def __init__(self, capacity: int, typ):
+        prog = ssz.compile_root(typ)
+        if ssz.is_fixed_size(typ) or not ssz.ragged_prog_ok(prog):
+            raise ValueError("a ragged list tree holds variable-size containers with a ragged root program")
+        self.typ = typ
+        self.capacity = int(capacity)
+        self._prog = np.ascontiguousarray(prog, dtype=np.uint32)
+        self._tree = ListTree(self.capacity, ssz.Bytes(32))
+
+    def close(self) -> None:
+        self._tree.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def count(self) -> int:
+        return self._tree.count
+
+    def __len__(self) -> int:
+        return self.count
+
+    def append(self, serialized_items) -> None:
+        """Appends the items' roots.  ValueError when an item breaks the offset rules (DESIGN.md
+        §7b.3) or the items do not fit; the tree is then unchanged."""
+        import torch
+        items = [bytes(x) for x in serialized_items]
+        n = len(items)
+        if n > self.capacity - self.count:
+            raise ValueError("the items do not fit the tree")
+        if n == 0:
+            return
+        L = _native.lib()
+        handle = self._tree._handle()
+        blob = b"".join(items)
+        starts = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in items], out=starts[1:])
+        d_items = torch.frombuffer(bytearray(blob or b"\x00"), dtype=torch.uint8).cuda()
+        d_starts = torch.from_numpy(starts).cuda()
+        d_roots = torch.empty(32 * n, dtype=torch.uint8, device="cuda")
+        d_status = torch.empty(n, dtype=torch.uint8, device="cuda")
+        d_bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+        ws = torch.empty(max(1, L.bls381_ssz_ragged_roots_workspace_size(n)), dtype=torch.uint8, device="cuda")
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _native.check(L.bls381_ssz_ragged_roots_device(
+            n, d_items.data_ptr(), len(blob), d_starts.data_ptr(), _ptr(self._prog), len(self._prog),
+            d_roots.data_ptr(), d_status.data_ptr(), d_bad.data_ptr(), ws.data_ptr(), stream))
+        # the bad count is read before the append is queued: a malformed item leaves the tree as it was
+        if int(d_bad.item()):
+            raise ValueError("%d malformed item(s); first at %d" % (int(d_bad.item()), int(d_status.argmax().item())))
+        ws2 = torch.empty(max(1, L.bls381_list_tree_append_workspace_size(handle, n)), dtype=torch.uint8, device="cuda")
+        _native.check(L.bls381_list_tree_append_device(handle, n, d_roots.data_ptr(), ws2.data_ptr(), stream))
+        torch.cuda.current_stream().synchronize()   # the scratch tensors go back to torch's allocator below
+
+    def clear(self) -> None:
+        """The empty list (the list-tree ABI has no reset: the tree is made anew)."""
+        self._tree.close()
+        self._tree = ListTree(self.capacity, ssz.Bytes(32))
+
+    def replace(self, serialized_items) -> None:
+        """The whole list becomes ``serialized_items`` (the epoch rotation's ``previous = current``
+        from the serialized attestations).  ValueError as for ``append``; the tree is then unchanged."""
+        new = RaggedListTree(self.capacity, self.typ)
+        try:
+            new.append(serialized_items)
+        except Exception:
+            new.close()
+            raise
+        self._tree.close()
+        self._tree = new._tree
+
+    def root(self) -> bytes:
+        """``hash_tree_root`` of the list."""
+        return self._tree.root(True)
+
+
 def validator_registry_tree(capacity: int) -> ListTree:
     """``state.validator_registry``: 121-byte Validator records."""
     return ListTree(capacity, ssz.Validator)

@@ -113,7 +113,8 @@ def build_hostcheck(force=False, sanitize=False, count_ops=False, defines=()):
         os.makedirs(SANITIZE_DIR, exist_ok=True)
     out = os.path.join(SANITIZE_DIR if (sanitize or defines) else LIB, name)
     src = os.path.join(CSRC, "host_check.cpp")
-    deps = [src, os.path.join(CSRC, "host_check_rewards.hpp"), os.path.join(CSRC, "host_check_regupd.hpp")] + [
+    deps = [src, os.path.join(CSRC, "host_check_rewards.hpp"), os.path.join(CSRC, "host_check_regupd.hpp"),
+            os.path.join(CSRC, "host_check_ssz_ragged.hpp")] + [
         os.path.join(CSRC, f) for f in HEADERS if f != "bls381_kernels.hpp"]
     if not force and _newer(out, deps):
         return out
@@ -156,6 +157,24 @@ def build_regupd_check(force=False):
         return out
     _run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
           "-static-libasan", "-static-libubsan", "-pthread", "-fno-omit-frame-pointer", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, src,
+          "-o", out])
+    return out
+
+
+def build_ssz_ragged_check(force=False):
+    """The stand-alone ASan/UBSan program over the ragged root programs of csrc/bls381_ssz.hpp
+    (csrc/ssz_ragged_check_main.cpp, its own main; tests/test_ssz_ragged_host.py runs it).  Out of
+    tree like the sanitized library."""
+    os.makedirs(SANITIZE_DIR, exist_ok=True)
+    out = os.path.join(SANITIZE_DIR, "ssz_ragged_check_asan")
+    src = os.path.join(CSRC, "ssz_ragged_check_main.cpp")
+    deps = [src] + [os.path.join(CSRC, f) for f in (
+        "host_check_ssz_ragged.hpp", "bls381_ssz.hpp", "bls381_merkle.hpp", "bls381_plan.hpp", "bls381_hash.hpp",
+        "bls381_curve.hpp", "bls381_field.hpp", "bls381_consts.hpp", "bls381_defs.hpp")]
+    if not force and _newer(out, deps):
+        return out
+    _run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+          "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, src,
           "-o", out])
     return out
 

@@ -1976,6 +1976,161 @@ int bls381_ssz_list_root(size_t n, const uint8_t* items, size_t item_size, const
   });
 }
 
+// ---- roots of variable-size items (the program and the rules: bls381_ssz.hpp)
+// the workspace of the ragged root kernel: the program and its error flag
+size_t bls381_ssz_ragged_roots_workspace_size(size_t n) {
+  return n > (size_t)INT32_MAX ? 0 : bls381_ssz_root_workspace_size();
+}
+
+// what the host can tell of a host-side `starts`: n + 1 non-decreasing offsets, every item below 2^32 bytes
+static bool ragged_starts_ok(size_t n, const uint64_t* starts) {
+  for (size_t i = 0; i < n; ++i)
+    if (starts[i + 1] < starts[i] || starts[i + 1] - starts[i] >= ((uint64_t)1 << 32)) return false;
+  return true;
+}
+
+// one launch whatever the items hold; d_n_bad (a device word, zeroed here) receives the count of bad items
+static int ragged_roots_impl(size_t n, const uint8_t* d_items, size_t items_bytes, const uint64_t* d_starts,
+                             const uint32_t* h_prog, uint32_t plen, uint8_t* d_roots, uint8_t* d_status,
+                             uint32_t* d_n_bad, const SszWs& w, hipStream_t s, Ctx* c) {
+  HIPC(hipMemsetAsync(d_n_bad, 0, 4, s));
+  if (n == 0) return 0;
+  Held<std::vector<uint32_t>> prog(c->keep, s, std::vector<uint32_t>(h_prog, h_prog + plen));
+  HIPC(hipMemcpyAsync(w.prog, prog->data(), 4 * plen, hipMemcpyHostToDevice, s));
+  HIPC(hipMemsetAsync(w.err, 0, 4, s));
+  LAUNCH("ssz_ragged_root", s, dim3(grid_for(n)), dim3(KBLOCK), k_ssz_ragged_root, n, d_items, items_bytes, d_starts,
+         (const uint32_t*)w.prog, plen, (const uint8_t*)c->ztab, d_roots, d_status, d_n_bad, w.err);
+  return 0;
+}
+
+int bls381_ssz_ragged_roots_device(size_t n, const uint8_t* d_items, size_t items_bytes, const uint64_t* d_starts,
+                                   const uint32_t* h_prog, uint32_t prog_len, uint8_t* d_roots32, uint8_t* d_status,
+                                   uint32_t* d_n_bad, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (n > (size_t)INT32_MAX || !ssz_ragged_prog_ok(h_prog, prog_len, 0) || !d_n_bad || !aligned4(d_n_bad) ||
+        !d_workspace || (n && (!d_starts || !d_roots32 || !d_status || (items_bytes && !d_items))) ||
+        !aligned4(d_roots32) || ((uintptr_t)d_starts & 7))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    Bump b(d_workspace, bls381_ssz_ragged_roots_workspace_size(n));
+    return ragged_roots_impl(n, d_items, items_bytes, d_starts, h_prog, prog_len, d_roots32, d_status, d_n_bad,
+                             carve_ssz(b), (hipStream_t)stream, c);
+  });
+}
+
+int bls381_ssz_ragged_roots(size_t n, const uint8_t* items, const uint64_t* starts, const uint32_t* prog,
+                            uint32_t prog_len, uint8_t* roots32, uint8_t* status) {
+  return guarded([&]() -> int {
+    if (n > (size_t)INT32_MAX || !ssz_ragged_prog_ok(prog, prog_len, 0) || (n && (!starts || !roots32 || !status)) ||
+        (n && !ragged_starts_ok(n, starts)) || (n && starts[n] != starts[0] && !items))
+      return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t bytes = (size_t)starts[n];
+    uint8_t *d_items, *d_roots, *d_status;
+    uint64_t* d_starts;
+    uint32_t* d_bad;
+    SszWs w;
+    TRY(hc.carve([&](Bump& b) {
+      d_items = b.take<uint8_t>(bytes);
+      d_starts = b.take<uint64_t>(n + 1);
+      d_roots = b.take<uint8_t>(32 * n);
+      d_status = b.take<uint8_t>(n);
+      d_bad = b.take<uint32_t>(1);
+      w = carve_ssz(b);
+    }));
+    TRY(hc.upload(d_items, items, bytes));
+    TRY(hc.upload(d_starts, starts, 8 * (n + 1)));
+    TRY(ragged_roots_impl(n, d_items, bytes, d_starts, prog, prog_len, d_roots, d_status, d_bad, w, hc.s, c));
+    TRY(hc.download(roots32, d_roots, 32 * n));
+    TRY(hc.download(status, d_status, n));
+    return hc.finish();
+  });
+}
+
+// hash_tree_root of a List / Vector of n variable-size elements: their roots, then the tiled tree
+// and the finish of bls381_ssz_list_root.  The launches depend on n alone.
+struct RaggedListWs {
+  uint8_t *roots, *status;
+  SszWs ssz;
+  MerkleWs merkle;
+};
+static RaggedListWs carve_ragged_list(Bump& b, const MerklePlan& p) {
+  RaggedListWs w;
+  w.roots = b.take<uint8_t>(32 * (size_t)p.n);
+  w.status = b.take<uint8_t>((size_t)p.n);
+  w.ssz = carve_ssz(b);
+  w.merkle = carve_merkle(b, p.node_bytes);
+  return w;
+}
+size_t bls381_ssz_ragged_list_root_workspace_size(size_t n) {
+  if (n > (size_t)INT32_MAX) return 0;
+  const MerklePlan p = plan_merkle(n, 0, merkle_chunk_depth(n), false);
+  return carved_bytes([&](Bump& b) { carve_ragged_list(b, p); });
+}
+
+int bls381_ssz_ragged_list_root_device(size_t n, const uint8_t* d_items, size_t items_bytes, const uint64_t* d_starts,
+                                       const uint32_t* h_prog, uint32_t prog_len, int mix_length, uint8_t* d_root32,
+                                       uint32_t* d_n_bad, void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (n > (size_t)INT32_MAX || !ssz_ragged_prog_ok(h_prog, prog_len, 0) || !d_root32 || !aligned4(d_root32) ||
+        !d_n_bad || !aligned4(d_n_bad) || !d_workspace || (n && (!d_starts || (items_bytes && !d_items))) ||
+        ((uintptr_t)d_starts & 7))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const MerklePlan p = plan_merkle(n, 0, merkle_chunk_depth(n), false);
+    Bump b(d_workspace, bls381_ssz_ragged_list_root_workspace_size(n));
+    const RaggedListWs w = carve_ragged_list(b, p);
+    TRY(ragged_roots_impl(n, d_items, items_bytes, d_starts, h_prog, prog_len, w.roots, w.status, d_n_bad, w.ssz, s, c));
+    return merkle_tree_impl(c, p, w.roots, w.merkle, mix_length, n, d_root32, s);
+  });
+}
+
+int bls381_ssz_ragged_list_root(size_t n, const uint8_t* items, const uint64_t* starts, const uint32_t* prog,
+                                uint32_t prog_len, int mix_length, uint8_t root[32], uint32_t* n_bad) {
+  return guarded([&]() -> int {
+    if (n > (size_t)INT32_MAX || !ssz_ragged_prog_ok(prog, prog_len, 0) || !root || (n && !starts) ||
+        (n && !ragged_starts_ok(n, starts)) || (n && starts[n] != starts[0] && !items))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = get_ctx(&rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t bytes = n ? (size_t)starts[n] : 0, wsb = bls381_ssz_ragged_list_root_workspace_size(n);
+    uint8_t *d_items, *d_root, *d_ws;
+    uint64_t* d_starts;
+    uint32_t* d_bad;
+    TRY(hc.carve([&](Bump& b) {
+      d_items = b.take<uint8_t>(bytes);
+      d_starts = b.take<uint64_t>(n + 1);
+      d_root = b.take<uint8_t>(32);
+      d_bad = b.take<uint32_t>(1);
+      d_ws = b.take<uint8_t>(wsb);
+    }));
+    TRY(hc.upload(d_items, items, bytes));
+    if (n) TRY(hc.upload(d_starts, starts, 8 * (n + 1)));
+    TRY(bls381_ssz_ragged_list_root_device(n, d_items, bytes, d_starts, prog, prog_len, mix_length, d_root, d_bad, d_ws,
+                                           hc.s));
+    uint32_t bad = 0;
+    uint8_t r[32];
+    TRY(hc.download(r, d_root, 32));
+    TRY(hc.download(&bad, d_bad, 4));
+    TRY(hc.finish());
+    if (n_bad) *n_bad = bad;
+    if (bad) return BLS381_EARG;   // a malformed item: the root is not the list's, and is not handed out
+    memcpy(root, r, 32);
+    return 0;
+  });
+}
+
 // n DepositData -> n Deposits under one root: the leaves hash_tree_root(data), the depth-32 tree
 // with every level kept, each leaf's proof written into its Deposit, the data copied behind it
 struct DepositsBuildWs {

@@ -85,5 +85,10 @@ constexpr size_t ML_L_WORDS_PER_ITEM = (size_t)ML_STEPS * ML_LC * FP_LIMBS * 2;
 enum : uint32_t { SSZ_CHUNK = 1, SSZ_MERKLE = 2 };
 constexpr int SSZ_STACK = 64;    // chunks
 constexpr int SSZ_PROG_MAX = 512;  // u32 words
+// ragged root programs: the ops over a variable-size item (bls381_ssz.hpp ssz_run_ragged)
+enum : uint32_t { SSZ_RAGGED = 3, SSZ_FIELD = 4, SSZ_ENTER = 5, SSZ_LEAVE = 6 };
+constexpr uint32_t SSZ_NO_NEXT = 0xffffffffu;   // "no next variable field": the field ends with its scope
+constexpr int SSZ_SCOPE_MAX = 4;                // nested variable-size containers, the item's own scope included
+constexpr uint32_t SSZ_FIXED_MAX = 1u << 16;    // bytes of a scope's fixed part
 
 }  // namespace bls381

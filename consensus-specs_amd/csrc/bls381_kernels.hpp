@@ -1490,6 +1490,36 @@ __global__ void __launch_bounds__(KBLOCK) k_ssz_root(size_t n, const uint8_t* __
     for (int b = 0; b < 4; ++b) o[4 * w + b] = (uint8_t)(r[w] >> (24 - 8 * b));
 }
 
+// roots of n serialized variable-size items, one lane each: item i is bytes [starts[i], starts[i+1])
+// of `items` and runs the ragged program (bls381_ssz.hpp ssz_run_ragged).  An item that breaks a
+// rule -- or whose range is not one: decreasing, past items_bytes, 2^32 bytes or more -- gets
+// status 1 and a zero root, counts into *n_bad, and is not read outside its range.  Lanes of a
+// wave run different trip counts (field lengths differ).  *err is set by a program the host check
+// would have rejected.
+__global__ void __launch_bounds__(KBLOCK) k_ssz_ragged_root(size_t n, const uint8_t* __restrict__ items,
+                                                            size_t items_bytes, const uint64_t* __restrict__ starts,
+                                                            const uint32_t* __restrict__ prog, uint32_t plen,
+                                                            const uint8_t* __restrict__ ztab,
+                                                            uint8_t* __restrict__ roots, uint8_t* __restrict__ status,
+                                                            uint32_t* n_bad, int32_t* __restrict__ err) {
+  const size_t i = item_index<1>();
+  if (i >= n) return;
+  uint32_t stk[SSZ_STACK][8];
+  uint32_t r[8];
+  const uint64_t lo = starts[i], hi = starts[i + 1];
+  int rc = SSZ_BAD_ITEM;
+  if (lo <= hi && hi <= items_bytes && hi - lo < ((uint64_t)1 << 32))
+    rc = ssz_run_ragged(r, items + lo, (uint32_t)(hi - lo), prog, plen, stk, (g_cu32*)ztab);
+  if (rc == SSZ_BAD_PROG) *err = 1;
+  if (rc != SSZ_OK) {
+    for (int w = 0; w < 8; ++w) r[w] = 0;
+    atomicAdd(n_bad, 1u);
+  }
+  status[i] = rc != SSZ_OK;
+  g_u32* o = (g_u32*)(roots + 32 * i);
+  for (int w = 0; w < 8; ++w) o[w] = __builtin_bswap32(r[w]);
+}
+
 // gather a byte field [off, off + len) of n strided items into a packed array
 __global__ void __launch_bounds__(KBLOCK) k_gather_field(size_t n, const uint8_t* __restrict__ items, size_t stride,
                                                          uint32_t off, uint32_t len, uint8_t* __restrict__ out) {

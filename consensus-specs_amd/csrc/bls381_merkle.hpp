@@ -74,14 +74,7 @@ BLS_DEV_INLINE void merkle_fold_step(uint32_t v[8], uint64_t first, uint32_t g, 
   sha256_pair(v, l, r);
 }
 
-// mix_in_length (ssz_impl.py:122-124): v = H(v || length as 32 bytes little-endian)
-BLS_DEV_INLINE void merkle_mix_in_length(uint32_t v[8], uint64_t length) {
-  uint32_t l[8], r[8];
-  for (int w = 0; w < 8; ++w) { l[w] = v[w]; r[w] = 0; }
-  r[0] = __builtin_bswap32((uint32_t)length);
-  r[1] = __builtin_bswap32((uint32_t)(length >> 32));
-  sha256_pair(v, l, r);
-}
+// (merkle_mix_in_length: bls381_ssz.hpp, whose ragged programs mix a field's length in)
 
 // where the tile keeps node i (i < MERKLE_TILE / 2) of a step, in words of one 8-plane row: even
 // nodes, 16 words of padding, odd nodes.  A lane's pair (2l, 2l + 1) is then at l and l + 80, and

@@ -487,6 +487,54 @@ inline bool ssz_prog_ok(const uint32_t* prog, uint32_t plen, size_t item_size) {
   }
   return sp == 1 && peak <= SSZ_STACK;
 }
+// the ragged counterpart (ssz_run_ragged): the same walk with the scopes.  Chunk reads and offset
+// words lie inside the fixed part of their scope (the item's bytes past it are the item's to
+// bound, at run time), scopes nest SSZ_SCOPE_MAX deep at most, a fixed part is at most
+// SSZ_FIXED_MAX bytes, and the stack holds the stream of the longest field the call admits:
+// max_field_bytes, or with 0 what a 32-bit offset can span (2^27 chunks, 28 entries).
+inline bool ssz_ragged_prog_ok(const uint32_t* prog, uint32_t plen, uint64_t max_field_bytes) {
+  if (!prog || plen < 2 || plen > SSZ_PROG_MAX || prog[0] != SSZ_RAGGED || prog[1] > SSZ_FIXED_MAX) return false;
+  if (max_field_bytes == 0 || max_field_bytes > 0xffffffffull) max_field_bytes = 0xffffffffull;
+  const uint64_t max_chunks = (max_field_bytes + 31) / 32;
+  int stream = 1;                                  // chunk_depth(max_chunks) + 1
+  while (((uint64_t)1 << (stream - 1)) < max_chunks) ++stream;
+  uint32_t fixed[SSZ_SCOPE_MAX] = {prog[1]};
+  int d = 0, sp = 0, peak = 0;
+  const auto word_in = [&](uint32_t pos) { return pos <= fixed[d] && fixed[d] - pos >= 4; };
+  for (uint32_t pc = 2; pc < plen;) {
+    const uint32_t op = prog[pc];
+    if (op == SSZ_CHUNK && pc + 2 < plen) {
+      if (prog[pc + 2] > 32 || (uint64_t)prog[pc + 1] + prog[pc + 2] > fixed[d]) return false;
+      ++sp; pc += 3;
+    } else if (op == SSZ_MERKLE && pc + 1 < plen) {
+      const uint32_t k = prog[pc + 1];
+      if (k == 0 || (int)k > sp) return false;
+      uint32_t p = 1;
+      while (p < k) p <<= 1;
+      if (sp - (int)k + (int)p > peak) peak = sp - (int)k + (int)p;
+      sp = sp - (int)k + 1; pc += 2;
+    } else if ((op == SSZ_FIELD || op == SSZ_ENTER) && pc + 3 < plen) {
+      const uint32_t next = prog[pc + 2], arg = prog[pc + 3];
+      if (!word_in(prog[pc + 1]) || (next != SSZ_NO_NEXT && !word_in(next))) return false;
+      if (op == SSZ_FIELD) {
+        if (arg == 0 || arg > 32 || (arg & (arg - 1))) return false;
+        if (sp + stream > peak) peak = sp + stream;
+        ++sp;
+      } else {
+        if (d + 1 >= SSZ_SCOPE_MAX || arg > SSZ_FIXED_MAX) return false;
+        fixed[++d] = arg;
+      }
+      pc += 4;
+    } else if (op == SSZ_LEAVE) {
+      if (d == 0) return false;
+      --d; pc += 1;
+    } else {
+      return false;
+    }
+    if (sp > peak) peak = sp;
+  }
+  return sp == 1 && d == 0 && peak <= SSZ_STACK;
+}
 // signing_root(DepositData) (0_beacon-chain.md:394-403; ssz_impl.py:158-163): pubkey Bytes48 (2 chunks),
 // withdrawal_credentials Bytes32, amount uint64; the signature field is left out
 constexpr uint32_t DEPOSIT_SIGNING_PROG[] = {SSZ_CHUNK, 0, 32, SSZ_CHUNK, 32, 16, SSZ_MERKLE, 2,

@@ -460,6 +460,49 @@ int bls381_ssz_list_root_device(size_t n, const uint8_t* d_items, size_t stride,
                                 const uint32_t* h_prog, uint32_t prog_len, int mix_length, uint8_t* d_root32,
                                 void* d_workspace, void* stream);
 
+/* Roots of n variable-size items in one call: attestations, pending and
+ * indexed attestations, attester slashings.  Item i is bytes [starts[i], starts[i+1]) of `items`:
+ * the SSZ serialization of a container whose variable-size fields are lists of basic elements
+ * (`bytes` included) or such containers again (ssz_impl.py:72-103: fixed parts with a 4-byte
+ * little-endian offset in place of each variable field, then the variable parts).  `prog` is the
+ * type compiled by bls381_amd/ssz.py: {3, fixed} opens it (the fixed part's bytes); {1, off, len}
+ * and {2, k} are as in bls381_ssz_root_batch, off inside the fixed part of the current scope;
+ * {4, pos, next, esz} pushes the root of the basic list whose offset word is at `pos` and which
+ * ends at the offset at `next` (0xffffffff: with the scope), elements of esz bytes, its length
+ * mixed in; {5, pos, next, fixed} enters the container at that field, {6} leaves it.
+ * Items are untrusted.  One is well formed when in every scope: the scope is at least as long as
+ * its fixed part; the first offset equals the fixed part's size; offsets do not decrease; the last
+ * is at most the scope's length; a field's length is a multiple of its element size.  A malformed
+ * item gets status[i] = 1 and an all-zero root (a well-formed one status 0), no byte outside its
+ * range is read for it, and the other items are unaffected.
+ *   roots        n x 32 bytes and n status bytes.
+ *   list_root    hash_tree_root of the list of the n items: the tree of depth ceil(log2 n) over
+ *                their roots, mix_in_length(n) when mix_length != 0; n == 0 gives the empty list's
+ *                root.  *n_bad (may be NULL in the host form) receives the count of malformed
+ *                items; the host form then returns BLS381_EARG and leaves root[] alone, the device
+ *                form leaves the count in the device word d_n_bad for the caller to look at (the
+ *                root is then that of the list with zero chunks for those items).
+ * Device forms take the offsets in device memory and items_bytes, the size of the d_items buffer:
+ * a range that decreases, ends past items_bytes or spans 2^32 bytes or more is a malformed item.
+ * They queue a number of launches that depends on n alone, never synchronise and read nothing back.
+ * BLS381_EARG, found on the host: a program that is not well formed (512 words, 64 chunks of stack
+ * with 28 for the longest field a 32-bit offset admits, scopes 4 deep, chunk reads and offset
+ * words inside the fixed part); host-form starts that decrease, or an item of 2^32 bytes or more;
+ * n above 2^31 - 1; a NULL pointer that is needed; d_roots32, d_root32 and d_n_bad not 4-byte or
+ * d_starts not 8-byte aligned. */
+size_t bls381_ssz_ragged_roots_workspace_size(size_t n);
+int bls381_ssz_ragged_roots(size_t n, const uint8_t* items, const uint64_t* starts, const uint32_t* prog,
+                            uint32_t prog_len, uint8_t* roots32, uint8_t* status);
+int bls381_ssz_ragged_roots_device(size_t n, const uint8_t* d_items, size_t items_bytes, const uint64_t* d_starts,
+                                   const uint32_t* h_prog, uint32_t prog_len, uint8_t* d_roots32, uint8_t* d_status,
+                                   uint32_t* d_n_bad, void* d_workspace, void* stream);
+size_t bls381_ssz_ragged_list_root_workspace_size(size_t n);
+int bls381_ssz_ragged_list_root(size_t n, const uint8_t* items, const uint64_t* starts, const uint32_t* prog,
+                                uint32_t prog_len, int mix_length, uint8_t root[32], uint32_t* n_bad);
+int bls381_ssz_ragged_list_root_device(size_t n, const uint8_t* d_items, size_t items_bytes, const uint64_t* d_starts,
+                                       const uint32_t* h_prog, uint32_t prog_len, int mix_length, uint8_t* d_root32,
+                                       uint32_t* d_n_bad, void* d_workspace, void* stream);
+
 /* n serialized DepositData (184 B each) -> n serialized Deposits (1,208 B: the 32-sibling proof,
  * then the data) under one deposit root: leaf first_index + i is hash_tree_root(data i), every
  * other leaf of the depth-32 tree is zero (the reference's test/helpers/deposits.py build, the
