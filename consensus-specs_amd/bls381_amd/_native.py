@@ -229,6 +229,23 @@ _SIGS = {
     "bls381_exit_queue": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64, _u8p, _u8p]),
     "bls381_exit_queue_device": (ctypes.c_int, [ctypes.c_size_t, _u8p, _u8p, ctypes.c_size_t, ctypes.c_uint64, _u8p,
                                                 _u8p, _u8p, _u8p]),
+    "bls381_fork_choice_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
+    "bls381_fork_choice_destroy": (None, [ctypes.c_void_p]),
+    "bls381_fork_choice_add_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_fork_choice_node": (ctypes.c_uint32, [ctypes.c_void_p, _u8p]),
+    "bls381_fork_choice_root": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, _u8p]),
+    "bls381_fork_choice_block_count": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "bls381_fork_choice_on_attestations_workspace_size": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "bls381_fork_choice_on_attestations": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, _u8p,
+                                                          _u8p]),
+    "bls381_fork_choice_on_attestations_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p,
+                                                                 _u8p, _u8p, _u8p, _u8p]),
+    "bls381_fork_choice_read_latest": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, _u8p, _u8p]),
+    "bls381_fork_choice_prune": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    "bls381_fork_choice_head": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, _u8p, _u8p, _u8p,
+                                               ctypes.c_size_t, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),
+    "bls381_fork_choice_head_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, _u8p, _u8p, _u8p,
+                                                      ctypes.c_size_t, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p]),
     "bls381_registry_create": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     "bls381_registry_destroy": (None, [ctypes.c_void_p]),
     "bls381_registry_size": (ctypes.c_size_t, [ctypes.c_void_p]),

@@ -20,7 +20,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_SOURCES = ["bls381_capi.hip"]
 HEADERS = ["bls381_defs.hpp", "bls381_consts.hpp", "bls381_field.hpp", "bls381_curve.hpp", "bls381_hash.hpp",
            "bls381_lazy.hpp", "bls381_pairing.hpp", "bls381_pair.hpp", "bls381_quad.hpp", "bls381_ssz.hpp",
-           "bls381_merkle.hpp", "bls381_deptree.hpp", "bls381_listtree.hpp", "bls381_shuffle.hpp", "bls381_epoch.hpp", "bls381_rewards.hpp", "bls381_regupd.hpp", "bls381_keytable.hpp", "bls381_plan.hpp", "bls381_scope.hpp", "bls381_kernels.hpp"]
+           "bls381_merkle.hpp", "bls381_deptree.hpp", "bls381_listtree.hpp", "bls381_shuffle.hpp", "bls381_epoch.hpp", "bls381_rewards.hpp", "bls381_regupd.hpp", "bls381_forkchoice.hpp", "bls381_keytable.hpp", "bls381_plan.hpp", "bls381_scope.hpp", "bls381_kernels.hpp"]
 
 
 def _newer(target, deps):
@@ -114,7 +114,7 @@ def build_hostcheck(force=False, sanitize=False, count_ops=False, defines=()):
     out = os.path.join(SANITIZE_DIR if (sanitize or defines) else LIB, name)
     src = os.path.join(CSRC, "host_check.cpp")
     deps = [src, os.path.join(CSRC, "host_check_rewards.hpp"), os.path.join(CSRC, "host_check_regupd.hpp"),
-            os.path.join(CSRC, "host_check_ssz_ragged.hpp")] + [
+            os.path.join(CSRC, "host_check_forkchoice.hpp"), os.path.join(CSRC, "host_check_ssz_ragged.hpp")] + [
         os.path.join(CSRC, f) for f in HEADERS if f != "bls381_kernels.hpp"]
     if not force and _newer(out, deps):
         return out
@@ -157,6 +157,22 @@ def build_regupd_check(force=False):
         return out
     _run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
           "-static-libasan", "-static-libubsan", "-pthread", "-fno-omit-frame-pointer", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, src,
+          "-o", out])
+    return out
+
+
+def build_forkchoice_check(force=False):
+    """The stand-alone ASan/UBSan program over csrc/bls381_forkchoice.hpp (csrc/forkchoice_check_main.cpp,
+    its own main; tests/test_fork_choice_host.py runs it).  Out of tree like the sanitized library."""
+    os.makedirs(SANITIZE_DIR, exist_ok=True)
+    out = os.path.join(SANITIZE_DIR, "forkchoice_check_asan")
+    src = os.path.join(CSRC, "forkchoice_check_main.cpp")
+    deps = [src] + [os.path.join(CSRC, f) for f in (
+        "host_check_forkchoice.hpp", "bls381_forkchoice.hpp", "bls381_epoch.hpp", "bls381_shuffle.hpp", "bls381_defs.hpp")]
+    if not force and _newer(out, deps):
+        return out
+    _run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+          "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC, src,
           "-o", out])
     return out
 

@@ -4120,6 +4120,316 @@ int bls381_registry_updates(size_t n, const uint8_t* activation_eligibility_epoc
   });
 }
 
+// ---- fork choice: latest messages and the LMD-GHOST head (bls381_forkchoice.hpp)
+// The tree, `seq` and `dirty` are the host's; the messages, the tree's numbering and the head's
+// scratch live in one device block carved at creation.
+struct FcDev {
+  unsigned long long *key, *sums;   // sums: direct weights (2 B words), then best_count (B), B = the blocks now
+  uint64_t *prefix, *count;
+  uint32_t *target, *numbering, *best_rank, *jump_a, *jump_b;   // numbering: parent, pre, sub, rank, node_at (B each)
+};
+static FcDev carve_fc(Bump& b, size_t vcap, size_t bcap) {
+  FcDev d;
+  d.key = b.take<unsigned long long>(vcap);
+  d.sums = b.take<unsigned long long>(3 * bcap);
+  d.prefix = b.take<uint64_t>(2 * (bcap + 1));
+  d.count = b.take<uint64_t>(bcap);
+  d.target = b.take<uint32_t>(vcap);
+  d.numbering = b.take<uint32_t>(5 * bcap);
+  d.best_rank = b.take<uint32_t>(bcap);
+  d.jump_a = b.take<uint32_t>(bcap);
+  d.jump_b = b.take<uint32_t>(bcap);
+  return d;
+}
+struct bls381_fork_choice {
+  int device = -1;
+  size_t vcap = 0, bcap = 0;
+  uint64_t seq = 0;
+  fc_tree tree;
+  bool dirty = true;   // the tree has changed since its numbering went to the device
+  void* block = nullptr;
+  FcDev d{};
+};
+
+int bls381_fork_choice_create(size_t validator_capacity, size_t block_capacity, bls381_fork_choice** out) {
+  if (!out) return BLS381_EARG;
+  *out = nullptr;
+  if (validator_capacity == 0 || (uint64_t)validator_capacity > 0xFFFFFFFFull || block_capacity == 0 ||
+      block_capacity > FC_BLOCK_LIMIT)
+    return BLS381_EARG;
+  int rc = 0;
+  Ctx* c = get_ctx(&rc);
+  if (!c) return rc;
+  std::unique_ptr<bls381_fork_choice> fc(new bls381_fork_choice());
+  fc->device = c->device;
+  fc->vcap = validator_capacity;
+  fc->bcap = block_capacity;
+  const size_t bytes = carved_bytes([&](Bump& b) { carve_fc(b, validator_capacity, block_capacity); });
+  bool ok = hipMalloc(&fc->block, bytes) == hipSuccess;
+  if (ok) {
+    Bump b(fc->block, bytes);
+    fc->d = carve_fc(b, validator_capacity, block_capacity);
+    ok = hipMemset(fc->d.key, 0, 8 * validator_capacity) == hipSuccess &&
+         hipMemset(fc->d.target, 0xFF, 4 * validator_capacity) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipFree(fc->block);
+    t_err = "fork choice allocation failed";
+    return BLS381_EHIP;
+  }
+  *out = fc.release();
+  return 0;
+}
+
+void bls381_fork_choice_destroy(bls381_fork_choice* fc) {
+  if (!fc) return;
+  (void)hipSetDevice(fc->device);
+  (void)hipDeviceSynchronize();   // calls queued on the caller's streams may still use the block
+  (void)hipFree(fc->block);
+  delete fc;
+}
+
+static Ctx* fc_ctx(const bls381_fork_choice* fc, int* rc) {
+  Ctx* c = get_ctx(rc);
+  if (c && c->device != fc->device) { t_err = "fork choice store belongs to another device"; *rc = BLS381_EARG; return nullptr; }
+  return c;
+}
+
+size_t bls381_fork_choice_block_count(const bls381_fork_choice* fc) { return fc ? fc->tree.size() : 0; }
+uint32_t bls381_fork_choice_node(const bls381_fork_choice* fc, const uint8_t root32[32]) {
+  return fc && root32 ? fc->tree.find(root32) : FC_NONE;
+}
+int bls381_fork_choice_root(const bls381_fork_choice* fc, uint32_t node, uint8_t root32[32]) {
+  if (!fc || !root32 || node >= fc->tree.size()) return BLS381_EARG;
+  std::memcpy(root32, fc->tree.root[node].data(), 32);
+  return 0;
+}
+
+int bls381_fork_choice_add_blocks(bls381_fork_choice* fc, size_t n, const uint8_t* roots32, const uint8_t* parent_roots32,
+                                  const uint64_t* slots, uint32_t* node_out) {
+  return guarded([&]() -> int {
+    if (!fc || (n && (!roots32 || !parent_roots32 || !slots))) return BLS381_EARG;
+    std::vector<uint32_t> ids(n);
+    const size_t before = fc->tree.size();
+    if (!fc->tree.add(n, roots32, parent_roots32, slots, fc->bcap, ids.data())) return BLS381_EARG;
+    if (fc->tree.size() != before) fc->dirty = true;
+    if (node_out) std::copy(ids.begin(), ids.end(), node_out);
+    return 0;
+  });
+}
+
+size_t bls381_fork_choice_on_attestations_workspace_size(size_t n_att) {
+  if ((uint64_t)n_att > FC_SEQ_LIMIT) return 0;
+  return carved_bytes([&](Bump& b) { b.take<fc_att>(n_att); });
+}
+
+int bls381_fork_choice_on_attestations_device(bls381_fork_choice* fc, size_t n_att, const uint32_t* h_att_off,
+                                              const uint32_t* d_entries, const uint64_t* h_slots,
+                                              const uint32_t* h_target_nodes, const uint8_t* d_ok, uint64_t* d_skipped,
+                                              void* d_workspace, void* stream) {
+  return guarded([&]() -> int {
+    if (!fc || !d_skipped || !aligned8(d_skipped) || !aligned4(d_entries) ||
+        (n_att && (!h_att_off || !h_slots || !h_target_nodes)))
+      return BLS381_EARG;
+    std::vector<fc_att> att;
+    if (n_att && !fc_plan_batch(n_att, h_att_off, h_slots, h_target_nodes, fc->tree.size(), fc->seq, &att)) return BLS381_EARG;
+    const size_t total = n_att ? (size_t)(h_att_off[n_att] - h_att_off[0]) : 0;
+    if (total && (!d_entries || !d_workspace)) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = fc_ctx(fc, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(hipMemsetAsync(d_skipped, 0, 8, s));
+    fc->seq += n_att;   // an attestation takes its number whether or not it leaves a message
+    if (total == 0) return 0;
+    Bump b(d_workspace, bls381_fork_choice_on_attestations_workspace_size(n_att));
+    fc_att* d_att = b.take<fc_att>(n_att);
+    Held<std::vector<fc_att>> hold(c->keep, s, std::move(att));
+    HIPC(hipMemcpyAsync(d_att, hold->data(), n_att * sizeof(fc_att), hipMemcpyHostToDevice, s));
+    const dim3 blk(EPOCH_BLOCK), grid(grid_for(total, EPOCH_BLOCK));
+    for (int pass = 0; pass < 2; ++pass)
+      LAUNCH("fc_attest", s, grid, blk, k_fc_attest, pass, (uint32_t)n_att, (const fc_att*)d_att, d_entries, d_ok,
+             (uint64_t)fc->vcap, fc->d.key, fc->d.target, (unsigned long long*)d_skipped);
+    return 0;
+  });
+}
+
+int bls381_fork_choice_on_attestations(bls381_fork_choice* fc, size_t n_att, const uint32_t* att_off, const uint32_t* entries,
+                                       const uint64_t* slots, const uint32_t* target_nodes, const uint8_t* ok,
+                                       uint64_t* skipped_out) {
+  return guarded([&]() -> int {
+    if (!fc || !skipped_out || (n_att && (!att_off || !slots || !target_nodes))) return BLS381_EARG;
+    const size_t end = n_att ? att_off[n_att] : 0;   // the device form checks the offsets before it queues anything
+    if (n_att && att_off[n_att] != att_off[0] && !entries) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = fc_ctx(fc, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    const size_t wsb = bls381_fork_choice_on_attestations_workspace_size(n_att);
+    uint32_t* d_ent;
+    uint8_t *d_ok, *d_ws;
+    uint64_t* d_skipped;
+    TRY(hc.carve([&](Bump& b) {
+      d_ent = b.take<uint32_t>(end + 1);
+      d_ok = b.take<uint8_t>(n_att + 1);
+      d_skipped = b.take<uint64_t>(1);
+      d_ws = b.take<uint8_t>(wsb + 1);
+    }));
+    if (entries) TRY(hc.upload(d_ent, entries, 4 * end));
+    if (ok) TRY(hc.upload(d_ok, ok, n_att));
+    TRY(bls381_fork_choice_on_attestations_device(fc, n_att, att_off, d_ent, slots, target_nodes, ok ? d_ok : nullptr,
+                                                  d_skipped, d_ws, hc.s));
+    uint64_t skipped = 0;
+    TRY(hc.download(&skipped, d_skipped, 8));
+    TRY(hc.finish());
+    *skipped_out = skipped;
+    return 0;
+  });
+}
+
+int bls381_fork_choice_read_latest(bls381_fork_choice* fc, size_t first, size_t n, uint64_t* slots_out,
+                                   uint32_t* targets_out) {
+  return guarded([&]() -> int {
+    if (!fc || first > fc->vcap || n > fc->vcap - first || (n && (!slots_out || !targets_out))) return BLS381_EARG;
+    if (n == 0) return 0;
+    int rc = 0;
+    Ctx* c = fc_ctx(fc, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    std::vector<uint64_t> keys(n);
+    std::vector<uint32_t> targets(n);
+    TRY(hc.download(keys.data(), fc->d.key + first, 8 * n));
+    TRY(hc.download(targets.data(), fc->d.target + first, 4 * n));
+    TRY(hc.finish());
+    for (size_t k = 0; k < n; ++k) slots_out[k] = fc_key_slot(keys[k]);
+    std::copy(targets.begin(), targets.end(), targets_out);
+    return 0;
+  });
+}
+
+int bls381_fork_choice_prune(bls381_fork_choice* fc, uint32_t new_anchor_node) {
+  return guarded([&]() -> int {
+    if (!fc || new_anchor_node >= fc->tree.size()) return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = fc_ctx(fc, &rc);
+    if (!c) return rc;
+    HIPC(hipDeviceSynchronize());   // calls queued on the caller's streams still use the old numbers
+    HostCall hc(c);
+    const size_t before = fc->tree.size();
+    uint32_t* d_map;
+    TRY(hc.carve([&](Bump& b) { d_map = b.take<uint32_t>(before); }));
+    std::vector<uint32_t> map;
+    fc->tree.prune(new_anchor_node, &map);
+    fc->dirty = true;
+    TRY(hc.upload(d_map, map.data(), 4 * before));
+    LAUNCH("fc_remap", hc.s, dim3(grid_for(fc->vcap, EPOCH_BLOCK)), dim3(EPOCH_BLOCK), k_fc_remap, (uint64_t)fc->vcap,
+           (const uint32_t*)d_map, fc->d.target);
+    return hc.finish();   // `map` is read by the copy until here
+  });
+}
+
+static bool fc_head_args_ok(const bls381_fork_choice* fc, uint32_t start_node, size_t n, const void* activation,
+                            const void* exit_, const void* effective, size_t stride) {
+  return fc && start_node < fc->tree.size() && n <= fc->vcap && field_ok(n, stride) &&
+         (n == 0 || (activation && exit_ && effective));
+}
+
+int bls381_fork_choice_head_device(bls381_fork_choice* fc, uint32_t start_node, size_t n, const uint8_t* d_activation_epoch,
+                                   const uint8_t* d_exit_epoch, const uint8_t* d_effective_balance, size_t stride,
+                                   uint64_t epoch, uint32_t* d_head_out, uint64_t* d_weights_out, uint64_t* d_status_out,
+                                   void* stream) {
+  return guarded([&]() -> int {
+    if (!fc_head_args_ok(fc, start_node, n, d_activation_epoch, d_exit_epoch, d_effective_balance, stride) || !d_head_out ||
+        !aligned4(d_head_out) || !aligned8(d_weights_out) || !d_status_out || !aligned8(d_status_out))
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = fc_ctx(fc, &rc);
+    if (!c) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = fc->tree.size();
+    const FcDev& d = fc->d;
+    if (fc->dirty) {   // O(blocks) on the host and one copy, only after the tree has changed
+      std::vector<uint32_t> pre, sub, node_at, rank, all(5 * B);
+      fc->tree.number(&pre, &sub, &node_at, &rank);
+      std::copy(fc->tree.parent.begin(), fc->tree.parent.end(), all.begin());
+      std::copy(pre.begin(), pre.end(), all.begin() + B);
+      std::copy(sub.begin(), sub.end(), all.begin() + 2 * B);
+      std::copy(rank.begin(), rank.end(), all.begin() + 3 * B);
+      std::copy(node_at.begin(), node_at.end(), all.begin() + 4 * B);
+      Held<std::vector<uint32_t>> hold(c->keep, s, std::move(all));
+      HIPC(hipMemcpyAsync(d.numbering, hold->data(), 4 * 5 * B, hipMemcpyHostToDevice, s));
+      fc->dirty = false;
+    }
+    const uint32_t *parent = d.numbering, *pre = parent + B, *sub = pre + B, *rank = sub + B, *node_at = rank + B;
+    unsigned long long *direct = d.sums, *best_count = d.sums + 2 * B;
+    HIPC(hipMemsetAsync(d.sums, 0, 8 * 3 * B, s));
+    HIPC(hipMemsetAsync(d.best_rank, 0, 4 * B, s));
+    HIPC(hipMemsetAsync(d_status_out, 0, 8 * FCS_WORDS, s));
+    const dim3 blk(EPOCH_BLOCK), nodes(grid_for(B, EPOCH_BLOCK));
+    if (n)
+      LAUNCH("fc_direct", s, dim3((unsigned)active_tiles(n), (unsigned)fc_node_tiles(B)), blk, k_fc_direct, (uint64_t)n,
+             (const uint32_t*)d.target, make_u64_field(d_activation_epoch, stride), make_u64_field(d_exit_epoch, stride),
+             make_u64_field(d_effective_balance, stride), epoch, (uint32_t)B, direct);
+    LAUNCH("fc_scan", s, dim3(1), blk, k_fc_scan, (uint32_t)B, node_at, (const unsigned long long*)direct, d.prefix);
+    LAUNCH("fc_count", s, nodes, blk, k_fc_count, (uint32_t)B, pre, sub, parent, (const uint64_t*)d.prefix, d.count,
+           d_weights_out, d.jump_a, best_count, (unsigned long long*)d_status_out);
+    for (int step = 0; step < 2; ++step)
+      LAUNCH("fc_best", s, nodes, blk, k_fc_best, step, (uint32_t)B, parent, rank, (const uint64_t*)d.count,
+             (const unsigned long long*)best_count, d.best_rank, d.jump_a);
+    // the rounds depend on the capacity alone
+    uint32_t *from = d.jump_a, *to = d.jump_b;
+    for (uint32_t r = 0, rounds = fc_rounds((uint32_t)fc->bcap); r < rounds; ++r) {
+      LAUNCH("fc_jump", s, nodes, blk, k_fc_jump, (uint32_t)B, (const uint32_t*)from, to, start_node,
+             r + 1 == rounds ? d_head_out : (uint32_t*)nullptr);
+      std::swap(from, to);
+    }
+    return 0;
+  });
+}
+
+int bls381_fork_choice_head(bls381_fork_choice* fc, uint32_t start_node, size_t n, const uint8_t* activation_epoch,
+                            const uint8_t* exit_epoch, const uint8_t* effective_balance, size_t stride, uint64_t epoch,
+                            uint32_t* head_out, uint8_t head_root32[32], uint64_t* weights_out, uint64_t* status_out) {
+  return guarded([&]() -> int {
+    if (!fc_head_args_ok(fc, start_node, n, activation_epoch, exit_epoch, effective_balance, stride) || !head_out ||
+        !status_out)
+      return BLS381_EARG;
+    int rc = 0;
+    Ctx* c = fc_ctx(fc, &rc);
+    if (!c) return rc;
+    HostCall hc(c);
+    HostFields hf;
+    hf.add(activation_epoch, stride);
+    hf.add(exit_epoch, stride);
+    hf.add(effective_balance, stride);
+    hf.plan(n);
+    const size_t B = fc->tree.size();
+    uint32_t* d_head;
+    uint64_t *d_weights, *d_status;
+    TRY(hc.carve([&](Bump& b) {
+      hf.carve(b);
+      d_weights = b.take<uint64_t>(B);
+      d_status = b.take<uint64_t>(FCS_WORDS);
+      d_head = b.take<uint32_t>(1);
+    }));
+    for (int g = 0; g < hf.ncopies; ++g) TRY(hc.upload(hf.dev_lo(g), hf.lo[g], hf.bytes[g]));
+    TRY(bls381_fork_choice_head_device(fc, start_node, n, hf.dev(0), hf.dev(1), hf.dev(2), stride, epoch, d_head,
+                                       weights_out ? d_weights : nullptr, d_status, hc.s));
+    uint32_t head = FC_NONE;
+    uint64_t status[FCS_WORDS];
+    TRY(hc.download(&head, d_head, 4));
+    TRY(hc.download(status, d_status, 8 * FCS_WORDS));
+    if (weights_out) TRY(hc.download(weights_out, d_weights, 8 * B));
+    TRY(hc.finish());
+    if (head >= B) { t_err = "fork choice head: no head came back"; return BLS381_EHIP; }
+    *head_out = head;
+    if (head_root32) std::memcpy(head_root32, fc->tree.root[head].data(), 32);
+    for (uint32_t x = 0; x < FCS_WORDS; ++x) status_out[x] = status[x];
+    return 0;
+  });
+}
+
 }  // extern "C"
 
 // ---- multi-GPU over RCCL: one process per GPU, a communicator

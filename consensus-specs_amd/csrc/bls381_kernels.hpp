@@ -19,6 +19,7 @@
 #include "bls381_epoch.hpp"
 #include "bls381_rewards.hpp"
 #include "bls381_regupd.hpp"
+#include "bls381_forkchoice.hpp"
 #include "bls381_keytable.hpp"
 
 namespace bls381 {
@@ -2760,6 +2761,217 @@ __global__ void __launch_bounds__(EPOCH_BLOCK) k_regupd_apply(uint64_t n, regupd
     const uint32_t at = tid == 0 ? RS_ELIGIBLE : tid == 1 ? RS_ACTIVATED : tid == 2 ? RS_CHANGED : RS_STATUS;
     if (c) atomicAdd(summary + at, (unsigned long long)c);
   }
+}
+
+// ------------------------------ fork choice: latest messages and the LMD-GHOST head (§7i) -----
+// (the key, the two-word sums and the host's numbering of the tree: bls381_forkchoice.hpp)
+// One lane per entry of a batch (n_att >= 1, the last attestation's end above the first one's
+// first).  pass 0: the maximum of the keys per validator; an entry at or above `capacity` is
+// skipped and counted.  pass 1, a launch later: the target where the validator's key is the
+// entry's own -- keys are unique per attestation, so lanes that write one validator write one
+// value.  ok == NULL: every attestation counts; else the members of one with ok[a] == 0 are not
+// looked at.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_fc_attest(int pass, uint32_t n_att, const fc_att* __restrict__ att,
+                                                           const uint32_t* __restrict__ entries,
+                                                           const uint8_t* __restrict__ ok, uint64_t capacity,
+                                                           unsigned long long* key, uint32_t* target,
+                                                           unsigned long long* skipped) {
+  __shared__ uint32_t wave_skipped[EPOCH_BLOCK / 64];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t base = att[0].first, total = att[n_att - 1].end - base;
+  const uint64_t at = (uint64_t)blockIdx.x * EPOCH_BLOCK + tid;
+  bool skip = false;
+  if (at < total) {
+    const uint32_t j = base + (uint32_t)at;
+    const uint32_t a = fc_att_of(att, n_att, j);
+    if (!ok || ok[a]) {
+      const uint32_t v = entries[j];
+      const unsigned long long mine = att[a].key;
+      if (v >= capacity) skip = true;
+      else if (pass == 0) atomicMax(key + v, mine);
+      else if (key[v] == mine) target[v] = att[a].target;
+    }
+  }
+  if (pass != 0) return;   // the same for the whole launch
+  const uint64_t m = __ballot(skip);
+  if ((tid & 63u) == 0) wave_skipped[tid >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t c = wave_skipped[0] + wave_skipped[1] + wave_skipped[2] + wave_skipped[3];
+    if (c) atomicAdd(skipped, (unsigned long long)c);
+  }
+}
+
+// prune: every validator's target through the old -> new table (FC_NONE where the block went)
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_fc_remap(uint64_t n, const uint32_t* __restrict__ map,
+                                                          uint32_t* __restrict__ target) {
+  const uint64_t i = (uint64_t)blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t t = target[i];
+  if (t != FC_NONE) target[i] = map[t];
+}
+
+// the sum of v over the wave's lanes (every lane active)
+BLS_DEV_INLINE unsigned long long fc_wave_sum(unsigned long long v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+#endif
+  return v;
+}
+
+// Direct weights.  Workgroup (x, y): validator tile x (as the active indices' tiles) against the
+// nodes [y FC_BINS, (y + 1) FC_BINS): a validator whose target lies elsewhere costs this workgroup
+// the 4 bytes of its target and no more.  Each lane sums runs of equal targets in registers, the
+// run it ends with is summed over the wave where the wave agrees on the target (most validators
+// vote for a handful of nodes), everything else is a ds add into the workgroup's bins, and each
+// non-empty word of the bins is one global add: direct[2 node] += low halves, [2 node + 1] += high.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_fc_direct(uint64_t n, const uint32_t* __restrict__ target,
+                                                           u64_field activation, u64_field exit_, u64_field effective,
+                                                           uint64_t epoch, uint32_t n_blocks, unsigned long long* direct) {
+  __shared__ unsigned long long bins[2 * FC_BINS];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t node0 = blockIdx.y * FC_BINS;
+  const uint32_t width = n_blocks - node0 < FC_BINS ? n_blocks - node0 : FC_BINS;   // node0 < n_blocks
+  for (uint32_t b = tid; b < 2 * width; b += EPOCH_BLOCK) bins[b] = 0;
+  __syncthreads();
+  uint32_t run = FC_NONE;   // the bin of the lane's open run
+  unsigned long long lo = 0, hi = 0;
+  for (uint32_t k = 0; k < ACTIVE_ROUNDS; ++k) {
+    const uint64_t i = active_item(blockIdx.x, k, tid);
+    if (i >= n) continue;
+    const uint32_t bin = target[i] - node0;   // FC_NONE and the nodes of other tiles land at or above width
+    if (bin >= width) continue;
+    if (!fc_votes(field_load(activation, (size_t)i), field_load(exit_, (size_t)i), epoch, node0 + bin)) continue;
+    const fc_sum s = fc_sum_of(field_load(effective, (size_t)i));
+    if (bin != run) {
+      if (run != FC_NONE) {
+        if (lo) atomicAdd(&bins[2 * run], lo);
+        if (hi) atomicAdd(&bins[2 * run + 1], hi);
+      }
+      run = bin;
+      lo = hi = 0;
+    }
+    lo += s.lo;
+    hi += s.hi;
+  }
+  // the runs left open: one add for the lanes that agree with the wave's first open run
+  const uint64_t open = __ballot(run != FC_NONE);
+  if (open) {   // the same on every lane of the wave
+    const uint32_t first = (uint32_t)__ffsll((unsigned long long)open) - 1;
+    const uint32_t lead = (uint32_t)__shfl((int)run, (int)first, 64);
+    const bool with = run == lead;
+    const unsigned long long wlo = fc_wave_sum(with ? lo : 0), whi = fc_wave_sum(with ? hi : 0);
+    if ((tid & 63u) == first) {
+      if (wlo) atomicAdd(&bins[2 * lead], wlo);
+      if (whi) atomicAdd(&bins[2 * lead + 1], whi);
+    } else if (run != FC_NONE && !with) {
+      if (lo) atomicAdd(&bins[2 * run], lo);
+      if (hi) atomicAdd(&bins[2 * run + 1], hi);
+    }
+  }
+  __syncthreads();
+  for (uint32_t b = tid; b < 2 * width; b += EPOCH_BLOCK)
+    if (bins[b]) atomicAdd(direct + 2 * (size_t)node0 + b, bins[b]);
+}
+
+// One workgroup: prefix[2 (p + 1) ..] = the two-word sum of the direct weights of the nodes at
+// preorder positions 0 .. p, FC_SCAN_TILE positions a round; prefix[0 .. 1] = 0.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_fc_scan(uint32_t n_blocks, const uint32_t* __restrict__ node_at,
+                                                         const unsigned long long* __restrict__ direct,
+                                                         uint64_t* __restrict__ prefix) {
+  __shared__ uint64_t scan_lo[FC_SCAN_TILE];
+  __shared__ uint64_t scan_hi[FC_SCAN_TILE];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t rounds = (n_blocks + FC_SCAN_TILE - 1) / FC_SCAN_TILE;
+  uint64_t carry_lo = 0, carry_hi = 0;
+  if (tid < 2) prefix[tid] = 0;
+  for (uint32_t r = 0; r < rounds; ++r) {
+    const uint32_t p = r * FC_SCAN_TILE + tid;
+    uint64_t lo = 0, hi = 0;
+    if (p < n_blocks) {
+      const size_t node = node_at[p];
+      lo = direct[2 * node];
+      hi = direct[2 * node + 1];
+    }
+    scan_lo[tid] = lo;
+    scan_hi[tid] = hi;
+    __syncthreads();
+    for (uint32_t d = 1; d < FC_SCAN_TILE; d <<= 1) {   // inclusive scans in place
+      const uint64_t vl = tid >= d ? scan_lo[tid - d] : 0, vh = tid >= d ? scan_hi[tid - d] : 0;
+      __syncthreads();
+      scan_lo[tid] += vl;
+      scan_hi[tid] += vh;
+      __syncthreads();
+    }
+    if (p < n_blocks) {
+      prefix[2 * ((size_t)p + 1)] = carry_lo + scan_lo[tid];
+      prefix[2 * ((size_t)p + 1) + 1] = carry_hi + scan_hi[tid];
+    }
+    carry_lo += scan_lo[FC_SCAN_TILE - 1];
+    carry_hi += scan_hi[FC_SCAN_TILE - 1];
+    __syncthreads();   // the scans are rewritten next round
+  }
+}
+
+// One lane per node: its count from the prefix sums (saturated and counted in status where it
+// passes 2^64 - 1), jump[b] = b, and the count into the parent's maximum (best_count, zeroed
+// before).  weights_out may be NULL.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_fc_count(uint32_t n_blocks, const uint32_t* __restrict__ pre,
+                                                          const uint32_t* __restrict__ sub,
+                                                          const uint32_t* __restrict__ parent,
+                                                          const uint64_t* __restrict__ prefix,
+                                                          uint64_t* __restrict__ count, uint64_t* __restrict__ weights_out,
+                                                          uint32_t* __restrict__ jump, unsigned long long* best_count,
+                                                          unsigned long long* status) {
+  __shared__ uint32_t wave_ovf[EPOCH_BLOCK / 64];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t b = blockIdx.x * EPOCH_BLOCK + tid;
+  bool ovf = false;
+  if (b < n_blocks) {
+    const size_t p0 = pre[b], p1 = p0 + sub[b];
+    const fc_sum s = fc_sum_sub(fc_sum{prefix[2 * p1], prefix[2 * p1 + 1]}, fc_sum{prefix[2 * p0], prefix[2 * p0 + 1]});
+    const uint64_t c = fc_sum_value(s, &ovf);
+    count[b] = c;
+    if (weights_out) weights_out[b] = c;
+    jump[b] = b;
+    const uint32_t p = parent[b];
+    if (p != FC_NONE && c) atomicMax(best_count + p, (unsigned long long)c);
+  }
+  const uint64_t m = __ballot(ovf);
+  if ((tid & 63u) == 0) wave_ovf[tid >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t c = wave_ovf[0] + wave_ovf[1] + wave_ovf[2] + wave_ovf[3];
+    if (c) atomicAdd(status + FCS_OVERFLOWS, (unsigned long long)c);
+  }
+}
+
+// step 0: among the children that hold their parent's largest count, the largest rank (best_rank,
+// zeroed before; ranks are stored plus one).  step 1, a launch later: the one child that holds
+// both becomes its parent's jump.
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_fc_best(int step, uint32_t n_blocks, const uint32_t* __restrict__ parent,
+                                                         const uint32_t* __restrict__ rank,
+                                                         const uint64_t* __restrict__ count,
+                                                         const unsigned long long* best_count, uint32_t* best_rank,
+                                                         uint32_t* jump) {
+  const uint32_t b = blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (b >= n_blocks) return;
+  const uint32_t p = parent[b];
+  if (p == FC_NONE || count[b] != best_count[p]) return;
+  if (step == 0) atomicMax(best_rank + p, rank[b] + 1u);
+  else if (best_rank[p] == rank[b] + 1u) jump[p] = b;
+}
+
+// One round of pointer doubling: to[b] = from[from[b]].  head_out != NULL (the last round):
+// head_out[0] = to[start].
+__global__ void __launch_bounds__(EPOCH_BLOCK) k_fc_jump(uint32_t n_blocks, const uint32_t* __restrict__ from,
+                                                         uint32_t* __restrict__ to, uint32_t start,
+                                                         uint32_t* __restrict__ head_out) {
+  const uint32_t b = blockIdx.x * EPOCH_BLOCK + threadIdx.x;
+  if (b >= n_blocks) return;
+  const uint32_t j = from[from[b]];
+  to[b] = j;
+  if (head_out && b == start) head_out[0] = j;
 }
 
 }  // namespace bls381

@@ -1547,5 +1547,8 @@ long hc_scope_scenario(const char* name, int fail_at, char* out, size_t cap) {
 // ---- registry updates (bls381_regupd.hpp): hc_exit_queue, hc_registry_updates
 #include "host_check_regupd.hpp"
 
+// ---- fork choice (bls381_forkchoice.hpp): hc_fork_choice_create .. hc_fork_choice_head
+#include "host_check_forkchoice.hpp"
+
 // ---- roots of variable-size items (bls381_ssz.hpp ssz_run_ragged): hc_ssz_ragged_root, hc_ssz_ragged_prog_ok
 #include "host_check_ssz_ragged.hpp"

@@ -1003,6 +1003,92 @@ int bls381_exit_queue_device(size_t n, const uint8_t* d_activation_epoch, const 
                              uint64_t current_epoch, const bls381_registry_constants* constants, uint64_t* d_queue,
                              void* d_workspace, void* stream);
 
+/* ---- fork choice: latest messages and the LMD-GHOST head ------------------- */
+/* lmd_ghost (0_fork-choice.md:78-103) with get_ancestor (:56-69) and the latest-attestation rule
+ * (:71-72) over a store that keeps the block tree on the host and one latest message per validator
+ * on the device.  One thread and one stream at a time use a store, or the
+ * caller orders them.  The store belongs to the device current at creation and holds 12 bytes per
+ * validator of validator_capacity and 80 bytes per block of block_capacity there.
+ *
+ * Blocks.  add_blocks appends n blocks (32-byte roots, 32-byte parent roots, slots) and writes their
+ * node ids to node_out (may be NULL).  The first block ever added is the anchor: its parent root is
+ * not looked at.  Ids are dense in insertion order, so a parent's id is below its children's.  A
+ * root that is already known returns the id it has.  BLS381_EARG, and no block of the call is
+ * added: an unknown parent, a slot not above the parent's, a slot at or above 2^32, more blocks
+ * than block_capacity.  node looks a root up (0xFFFFFFFF: unknown), root gives a node's root,
+ * block_count the number of nodes.
+ *
+ * Latest messages.  A message is the key (slot << 32) | (0xFFFFFFFF - seq) and a target node
+ * (0xFFFFFFFF: none); seq numbers the attestations over the life of the store in the order they
+ * were handed in, and the larger key wins: the highest slot, and among equal slots the attestation
+ * handed in first.  Slots and seq stay below 2^32: a slot at or above 2^32, or an attestation that
+ * would be number 2^32 - 1 or later, is BLS381_EARG.
+ * on_attestations: attestation a (slot slots[a], target node target_nodes[a]) has the validators
+ * entries[att_off[a] .. att_off[a+1]) as members (att_off: n_att + 1 ascending entries).  With the
+ * arrays of bls381_attesting_entries_device, att_off[a] = group_key_off[2 a] and d_entries goes in
+ * as it is.  att_off, slots and target_nodes are host memory in both forms; entries and ok are
+ * device memory in the _device form.  ok may be NULL; else the members of an attestation with
+ * ok[a] == 0 (a verdict of the grouped verify, which the device form reads when the kernels run)
+ * are not looked at, and the attestation still takes its seq.  A member at or above
+ * validator_capacity is skipped and counted in *skipped (written by the call; the device form
+ * writes d_skipped).  The result does not depend on the order in which the device visits members.
+ * BLS381_EARG, and nothing changes: descending att_off, a target node that is not in the tree, the
+ * slot and seq bounds above, a NULL argument that is needed (the store and skipped always; the
+ * three host arrays when n_att is not 0; entries and the workspace when there are members),
+ * d_entries not 4-byte or d_skipped not 8-byte aligned.  The workspace holds
+ * bls381_fork_choice_on_attestations_workspace_size(n_att) bytes (0 above 2^32 - 1 attestations).
+ * read_latest: slots_out[k] = the slot of validator first + k's message (0 when it never had one),
+ * targets_out[k] its target node.  first + n above validator_capacity is BLS381_EARG.
+ *
+ * prune(new_anchor_node): the subtree of that node stays, renumbered in insertion order (the new
+ * anchor is node 0), the rest of the tree goes; a message whose target went keeps its key and gets
+ * target none.  Waits for the device, runs one pass over the messages, returns synchronised.
+ *
+ * head: validator i < n votes with effective_balance[i] for its target when activation_epoch[i] <=
+ * epoch < exit_epoch[i] and it has a message.  The fields are little-endian uint64 at base + i *
+ * stride as in the epoch context (121 with bases records + 88 / 96 / 113, or 8 over plain arrays);
+ * they are the columns of the start state, which for the spec's head is the justified state.  A
+ * block's vote count is the sum of the votes whose target is the block or a descendant
+ * (get_ancestor(target, block.slot) == block).  The head is reached from start_node by taking the
+ * child with the largest (vote count, root as a byte string) until a node has no child.
+ * head_out / d_head_out: the head's node id; head_root32 (host form, may be NULL): its root;
+ * weights_out / d_weights_out (may be NULL): the vote count of every node, block_count entries;
+ * status_out / d_status_out: one word, the number of nodes whose vote count would pass 2^64 - 1
+ * and reads 2^64 - 1.  Fields of validators without a message are not read.
+ * BLS381_EARG, and nothing is written: start_node not in the tree, n above validator_capacity, a
+ * stride below 8, a NULL argument that is needed (the store, head_out and status_out always; the
+ * fields when n is not 0), d_head_out not 4-byte or d_weights_out / d_status_out not 8-byte aligned.
+ * The device form queues a number of launches that depends on block_capacity alone (its
+ * ceil(log2(block_capacity)) rounds of pointer doubling), uploads the tree's numbering when the tree
+ * has changed since the last head, never synchronises and reads nothing back.  The host forms
+ * stage, run on the engine's stream and return synchronised. */
+typedef struct bls381_fork_choice bls381_fork_choice;
+int bls381_fork_choice_create(size_t validator_capacity, size_t block_capacity, bls381_fork_choice** out);
+void bls381_fork_choice_destroy(bls381_fork_choice* fc);
+int bls381_fork_choice_add_blocks(bls381_fork_choice* fc, size_t n, const uint8_t* roots32, const uint8_t* parent_roots32,
+                                  const uint64_t* slots, uint32_t* node_out);
+uint32_t bls381_fork_choice_node(const bls381_fork_choice* fc, const uint8_t root32[32]);
+int bls381_fork_choice_root(const bls381_fork_choice* fc, uint32_t node, uint8_t root32[32]);
+size_t bls381_fork_choice_block_count(const bls381_fork_choice* fc);
+size_t bls381_fork_choice_on_attestations_workspace_size(size_t n_att);
+int bls381_fork_choice_on_attestations(bls381_fork_choice* fc, size_t n_att, const uint32_t* att_off, const uint32_t* entries,
+                                       const uint64_t* slots, const uint32_t* target_nodes, const uint8_t* ok,
+                                       uint64_t* skipped_out);
+int bls381_fork_choice_on_attestations_device(bls381_fork_choice* fc, size_t n_att, const uint32_t* h_att_off,
+                                              const uint32_t* d_entries, const uint64_t* h_slots,
+                                              const uint32_t* h_target_nodes, const uint8_t* d_ok, uint64_t* d_skipped,
+                                              void* d_workspace, void* stream);
+int bls381_fork_choice_read_latest(bls381_fork_choice* fc, size_t first, size_t n, uint64_t* slots_out,
+                                   uint32_t* targets_out);
+int bls381_fork_choice_prune(bls381_fork_choice* fc, uint32_t new_anchor_node);
+int bls381_fork_choice_head(bls381_fork_choice* fc, uint32_t start_node, size_t n, const uint8_t* activation_epoch,
+                            const uint8_t* exit_epoch, const uint8_t* effective_balance, size_t stride, uint64_t epoch,
+                            uint32_t* head_out, uint8_t head_root32[32], uint64_t* weights_out, uint64_t* status_out);
+int bls381_fork_choice_head_device(bls381_fork_choice* fc, uint32_t start_node, size_t n, const uint8_t* d_activation_epoch,
+                                   const uint8_t* d_exit_epoch, const uint8_t* d_effective_balance, size_t stride,
+                                   uint64_t epoch, uint32_t* d_head_out, uint64_t* d_weights_out, uint64_t* d_status_out,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
