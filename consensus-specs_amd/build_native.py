@@ -4,7 +4,8 @@
 * lib/libbls381_hostcheck.so  -- test infrastructure: g++ build of the same arithmetic headers
 * lib/libbls381_devcheck.so   -- test infrastructure: gfx950 probe kernels over the lane-pair / quad / octet headers
 * lib/libbls381_rbcheck.so    -- test infrastructure: the randomized batch's own scalar-side kernels, every intermediate handed back
-* tools/valu_peak             -- integer-VALU peak microbenchmark (roofline denominator)
+* lib/libbls381_hashcheck.so  -- test infrastructure: hash_to_G2's search kernels, each route's offsets, candidates and points handed back
+* tools/valu_peak          -- integer-VALU peak microbenchmark (roofline denominator)
 """
 import os
 import subprocess
@@ -53,6 +54,12 @@ def build_rbcheck(force=False):
     """The randomized-batch probe library (csrc/rb_check.hip): the product's kernels header and hipcc flags."""
     deps = [os.path.join(CSRC, f) for f in ["rb_check.hip"] + HEADERS] + [os.path.join(INC, "bls381.h")]
     return _hipcc_shared(os.path.join(LIB, "libbls381_rbcheck.so"), ["rb_check.hip"], deps, force)
+
+
+def build_hashcheck(force=False):
+    """The hash_to_G2 search probe library (csrc/hash_check.hip): the product's kernels header and hipcc flags."""
+    deps = [os.path.join(CSRC, f) for f in ["hash_check.hip"] + HEADERS] + [os.path.join(INC, "bls381.h")]
+    return _hipcc_shared(os.path.join(LIB, "libbls381_hashcheck.so"), ["hash_check.hip"], deps, force)
 
 
 def _hipcc_shared(out, sources, deps, force=False, extra=()):
@@ -212,3 +219,4 @@ if __name__ == "__main__":
     build_hip(force)
     build_devcheck(force)
     build_rbcheck(force)
+    build_hashcheck(force)

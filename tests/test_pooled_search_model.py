@@ -1,48 +1,12 @@
 """Model of k_hash_cand_1's pooled try-and-increment search (bls381_kernels.hpp,
-dev_hash_cand_1): the lane assignment and per-item resolution, simulated for a 64-lane wave
-over random square patterns.  Each item must end with its lowest square offset -- the
+dev_hash_cand_1; the model: tests/pooled_search_model.py): the lane assignment and per-item
+resolution, simulated for a 64-lane wave over random square patterns.  Each item must end with its lowest square offset -- the
 spec's candidate order (bls_signature.md:74-86) -- whatever the other items do, and the
 wave must finish in far fewer rounds than a lane-per-item loop's slowest item.
 """
 import random
 
-
-def nth_set_bit(m, r):
-    for b in range(64):
-        if (m >> b) & 1:
-            if r == 0:
-                return b
-            r -= 1
-    raise AssertionError("rank out of range")
-
-
-def pooled_search(is_square, valid):
-    """is_square(item, offset) -> bool; valid[lane]; returns (found offsets, rounds)"""
-    k = [0] * 64
-    found = [-1 if valid[i] else 0 for i in range(64)]
-    rounds = 0
-    while True:
-        P = sum(1 << i for i in range(64) if found[i] < 0)
-        if P == 0:
-            return found, rounds
-        rounds += 1
-        m = bin(P).count("1")
-        t = [nth_set_bit(P, lane % m) for lane in range(64)]
-        off = [k[t[lane]] + lane // m for lane in range(64)]
-        B = sum(1 << lane for lane in range(64) if is_square(t[lane], off[lane]))
-        for lane in range(64):
-            if found[lane] < 0:
-                r = bin(P & ((1 << lane) - 1)).count("1")
-                first, cnt, j = -1, 0, r
-                while j < 64:
-                    if first < 0 and (B >> j) & 1:
-                        first = cnt
-                    j += m
-                    cnt += 1
-                if first >= 0:
-                    found[lane] = k[lane] + first
-                else:
-                    k[lane] += cnt
+from pooled_search_model import pooled_search
 
 
 def test_pooled_search_finds_first_square():
